@@ -4,10 +4,14 @@ hypergraph (BASELINE.json configs[2]).
 
 One step = one training epoch (forward + backward + Keras Adagrad over every
 HOBE record, batch 256, fresh device shuffle) with the records, tables and
-incidence already resident in HBM. Reported beside it, from the same run:
-  * "roofline": the dominant kernel (the fused one-launch batch step) in
-    algorithmic GB/s against the 8 TB/s HBM peak, HBM traffic per launch
-    from the committed PMC run of this bench;
+incidence already resident in HBM. A plain run builds the graph, samples the
+records, warms up, times the steps and prints the result line (`metric`,
+`value`, `unit`, `ms_per_step`, ...); "roofline" comes from the timed steps
+themselves: the dominant kernel (the fused one-launch batch step) in
+algorithmic GB/s against the 8 TB/s HBM peak, HBM traffic per launch from
+the committed PMC run of this bench. `--dump-outputs DIR` writes what the
+last timed step returned (dump_outputs below). Every other measurement runs
+only with `--full` (its key in the result line is null without it):
   * "cpu_baseline": the Keras-semantics trainer restated in C with OpenMP
     (oracle/cpu_train_mt.c) on a bounded slice of the same records;
   * "algdist": the relaxation (k=10, 20 iterations) in algorithmic GB/s;
@@ -28,7 +32,8 @@ incidence already resident in HBM. Reported beside it, from the same run:
     one training epoch, the CPU port on a slice of the same stream with
     tables of the same size.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py --full [--gpus N] [--steps K] [--warmup W]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 Multi-GPU: alg-dist is node-row sharded with RCCL all-reduces
@@ -49,9 +54,10 @@ then killed). A `--gpus` that disagrees with WORLD_SIZE is refused. The
 line carries `ranks_seen` (dist.get_world_size()) and `devices_seen`
 (torch.cuda.device_count()).
 
-`c4_full` (in the default run at N = 1, ~4.5 min of its ~7.5, started only
+`c4_full` (in the `--full` run at N = 1, ~4.5 min of its ~7.5, started only
 if it still fits `--time-budget`, 600 s; `--no-c4-full` skips it,
-`--c4-full` forces it, also at N > 1): the WHOLE C4 pipeline --
+`--c4-full` forces it, also at N > 1 and without `--full`): the WHOLE C4
+pipeline --
 alg-dist (k=10, 20 iterations; sharded at N > 1), HOBE sampling of every row
 into the record store, one global-shuffle d=256 epoch from the store
 (embedding.py:389-416's path) -- timed as `c4_full_time_to_embedding_s`.
@@ -102,6 +108,15 @@ def parse():
                       "pipelined over (1 = one all-reduce per iteration)")
   p.add_argument("--steps", type=int, default=3)
   p.add_argument("--warmup", type=int, default=1)
+  p.add_argument("--full", action="store_true",
+                 help="also run every other measurement (alg-dist, CPU "
+                      "baselines, C2 FOBE, MT19937 streams, end to end, the "
+                      "C4 / C5 legs, the whole-C4 pipeline); without it only "
+                      "the timed steps run")
+  p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                 help="after the timed steps write what the last step "
+                      "returned (its epoch losses and a seeded row sample of "
+                      "the trained tables) as DIR/<name>.npy")
   p.add_argument("--dim", type=int, default=128)
   p.add_argument("--num-samples", type=int, default=200)
   p.add_argument("--num-neighbors", type=int, default=5)
@@ -139,7 +154,10 @@ def parse():
                       "gloo only to rehearse several ranks on one GPU)")
   p.add_argument("--one-device", action="store_true",
                  help="every rank uses GPU 0 (rehearsal on a 1-GPU box)")
-  return p.parse_args()
+  args = p.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    p.error("--steps must be >= 1 and --warmup >= 0")
+  return args
 
 
 # the process's CPU share, read before any OpenMP runtime binds this thread:
@@ -350,6 +368,26 @@ def launch_selftest(mode, world, rank):
   dist.destroy_process_group()
 
 
+DUMP_TABLE_BYTES = 24 << 20  # per table; the two tables + losses < 64 MB
+
+
+def dump_outputs(out_dir, ctx, losses):
+  """--dump-outputs: what the last timed step handed back, as float32 .npy
+  files: `losses` (the epoch losses ctx.train returned) and `node_table` /
+  `edge_table` (the tables it trained; of a table larger than
+  DUMP_TABLE_BYTES a fixed seeded sample of rows, in ascending row order,
+  the same rows in every run)."""
+  os.makedirs(out_dir, exist_ok=True)
+  np.save(os.path.join(out_dir, "losses.npy"), np.asarray(losses, np.float32))
+  cap = max(1, DUMP_TABLE_BYTES // (4 * ctx.d))
+  rs = np.random.RandomState(20240)
+  for t, (name, rows) in enumerate((("node_table", ctx.node_rows),
+                                    ("edge_table", ctx.edge_rows))):
+    sel = (np.arange(rows) if rows <= cap
+           else np.sort(rs.choice(rows, cap, replace=False)))
+    np.save(os.path.join(out_dir, name + ".npy"), ctx.model_get_rows(t, sel))
+
+
 def main():
   args = parse()
   env_world = os.environ.get("WORLD_SIZE")
@@ -422,10 +460,13 @@ def main():
   y0 = rs.random_sample((inc.E, k))
   bytes_iter = 8.0 * inc.nnz + (8.0 + 12.0 * k) * (inc.N + inc.E)
 
-  # ---- algebraic distance (SpMV relaxation) ----
-  progress('C3 graph built; alg-dist')
+  # ---- algebraic distance (SpMV relaxation), --full ----
+  progress('C3 graph built' + ('; alg-dist' if args.full else ''))
   exch = {}
-  if world > 1:
+  alg_ms = alg_gbps = None
+  if not args.full:
+    pass
+  elif world > 1:
     alg_dist_sharded(ctx, inc, x0, y0, args.alg_iters)  # warm
     runs = [alg_dist_sharded(ctx, inc, x0, y0, args.alg_iters, stats=exch)[2]
             for _ in range(3)]
@@ -439,7 +480,8 @@ def main():
       ctx.alg_run(args.alg_iters)
       runs.append(ctx.alg_stats()[0])
     alg_ms = float(np.median(runs))
-  alg_gbps = bytes_iter * args.alg_iters / (alg_ms * 1e-3) / 1e9
+  if alg_ms is not None:
+    alg_gbps = bytes_iter * args.alg_iters / (alg_ms * 1e-3) / 1e9
 
   # ---- HOBE records (alg coords resident on the device) ----
   progress('C3 HOBE sampling')
@@ -471,8 +513,9 @@ def main():
   dev_ms = 0.0
   batches = fused_b = split_b = 0
   for s in range(args.steps):
-    ctx.train(batch=args.batch, max_epochs=1, loss=_hgx.LOSS_MSE,
-              act=_hgx.ACT_RELU, min_delta=-1e30, shuffle_seed=200 + s)
+    last_losses = ctx.train(batch=args.batch, max_epochs=1, loss=_hgx.LOSS_MSE,
+                            act=_hgx.ACT_RELU, min_delta=-1e30,
+                            shuffle_seed=200 + s)
     ms, rec, bat = ctx.train_stats()
     fz, sp = ctx.train_path_stats()
     dev_ms += ms
@@ -484,6 +527,8 @@ def main():
   elapsed = max_over_ranks(time.perf_counter() - t0)
   records = n * args.steps * world
   value = records / elapsed
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, ctx, last_losses)
 
   # ---- roofline of the dominant kernel: one batch step (train_step; K1 + K2
   # only where the step does not apply) ----
@@ -513,7 +558,7 @@ def main():
   # threads, unique rows updated in parallel) on the box's CPU share, plus
   # the single-threaded restatement oracle/hgref.c for reference.
   cpu = None
-  if rank == 0 and world == 1 and not args.no_cpu:
+  if args.full and rank == 0 and world == 1 and not args.no_cpu:
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import oracle as O
     threads = cpu_threads()
@@ -591,9 +636,9 @@ def main():
         "gpu_records_per_s": round(n / sample_s, 1) if sample_s > 0 else None}
 
   # ---- C2: FOBE d=128 on the same graph (BASELINE configs[1]) ----
-  progress('C2 FOBE + end-to-end legs')
   c2 = e2e = c3mt = None
-  if not args.no_extra:
+  if args.full and not args.no_extra:
+    progress('C2 FOBE + end-to-end legs')
     S, K = args.num_samples, args.num_neighbors
     q_n = np.full(inc.N, S, np.int32)  # int(weight * S), weights 1
     q_e = np.full(inc.E, S, np.int32)
@@ -695,11 +740,12 @@ def main():
 
   # ---- power-law 10M/5M graph (C4 shape) ----
   c4 = None
-  if not args.no_c4:
+  if args.full and not args.no_c4:
     progress("C4 legs (alg-dist, 2% HOBE d=256 slice, C5 combiner)")
     c4 = bench_c4(args, ctx, rank, world, sync, max_over_ranks, alg_dist_sharded)
   c4_full = None
-  if args.c4_full or (world == 1 and not args.no_c4 and not args.no_c4_full):
+  if args.c4_full or (args.full and world == 1 and not args.no_c4
+                      and not args.no_c4_full):
     spent = time.time() - T_START
     if not args.c4_full and spent + C4_FULL_EST_S > args.time_budget:
       # the default leg would not fit the run's time budget on this box
@@ -753,14 +799,16 @@ def main():
         },
         "roofline": roofline,
         "cpu_baseline": cpu,
-        "algdist": {"k": k, "iters": args.alg_iters,
-                    "ms_per_iter": round(alg_ms / args.alg_iters, 4),
-                    "gbps": round(alg_gbps, 1),
-                    "bytes_per_iter": bytes_iter,
-                    "frac_of_hbm_peak": round(alg_gbps / HBM_PEAK_GBPS, 4),
-                    "note": "C3's 35 MB working set is cache-resident; the "
-                            "HBM fraction is judged on algdist_c4",
-                    "sharded": world > 1, "exchange": exch or None},
+        "full": args.full,
+        "algdist": None if alg_ms is None else {
+            "k": k, "iters": args.alg_iters,
+            "ms_per_iter": round(alg_ms / args.alg_iters, 4),
+            "gbps": round(alg_gbps, 1),
+            "bytes_per_iter": bytes_iter,
+            "frac_of_hbm_peak": round(alg_gbps / HBM_PEAK_GBPS, 4),
+            "note": "C3's 35 MB working set is cache-resident; the "
+                    "HBM fraction is judged on algdist_c4",
+            "sharded": world > 1, "exchange": exch or None},
         "hobe_sampling_s": round(sample_s, 3),
         "sampling": ("row-sharded over ranks + record all-gather" if world > 1
                      else "single GPU"),

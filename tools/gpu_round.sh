@@ -16,9 +16,9 @@ timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smo
 echo smoke-ok
 fi
 [ $PART = tests ] && exit 0
-timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err || exit 14
+timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err || exit 14
 echo bench-ok
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof_bench -o run --output-format csv -- python3 bench.py --no-cpu --no-c4-full > $O/bench_prof.json 2> $O/bench_prof.err || exit 15
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof_bench -o run --output-format csv -- python3 bench.py --full --no-cpu --no-c4-full > $O/bench_prof.json 2> $O/bench_prof.err || exit 15
 find $O/prof_bench -name '*stats.csv' -exec cp {} $O/ \;
 rm -rf $O/prof_bench
 echo prof-ok
@@ -33,5 +33,5 @@ python tools/pmc_train_summary.py "$F" "$W" $O/pmc_train.json 128 6 > /dev/null 
 rm -rf $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE
 # the --gpus N path rehearsed on one GPU: bench.py starts its 2 ranks itself
 # (gloo on cuda:0; not a scaling measurement: both ranks share one GPU)
-timeout -k 10 600 python3 -u bench.py --gpus 2 --steps 1 --warmup 0 --one-device --dist-backend gloo --no-cpu --no-extra > $O/bench_2rank_gloo.json 2> $O/bench_2rank_gloo.err || { echo G2FAIL; exit 19; }
+timeout -k 10 600 python3 -u bench.py --full --gpus 2 --steps 1 --warmup 0 --one-device --dist-backend gloo --no-cpu --no-extra > $O/bench_2rank_gloo.json 2> $O/bench_2rank_gloo.err || { echo G2FAIL; exit 19; }
 echo all-ok
