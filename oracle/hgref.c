@@ -816,7 +816,8 @@ void hgref_jaccard_probs(int kind, int64_t n, const int32_t *pa,
 /* Trainer: BooleanModel (hg2v_model.py:51-125, sigmoid heads + KLD) and      */
 /* UnweightedFloatModel (:129-203, relu heads + MSE), fit loop of            */
 /* embedding.py:269-305 -- Keras 2.x semantics restated (PARITY UNPINNED:    */
-/* keras/tensorflow are absent):                                             */
+/* keras/tensorflow are absent; the backward pass and the Adagrad step are   */
+/* pinned to a float64 autograd restatement, tests/hg2v_autograd.py):        */
 /*   heads nn = act(N[ln].N[rn]), ee = act(E[le].E[re]),                      */
 /*         ne = mean_k act(N[nn_k].N[ln]) * mean_k act(E[ne_k].E[re]);       */
 /*   loss = sum over heads of batch-mean; KLD = yt'*log(yt'/yp') with         */
