@@ -31,7 +31,12 @@ from .proto_native import (ShardedEmbedding, read_embedding, read_incidence,
 from .combine_embeddings_util import (CombineEmbeddingsViaConcatenation,
                                       CombineEmbeddingsViaNodeEdgeClassifier)
 from .evaluation_util import (EXPERIMENT_OPTIONS, CalculateCommunityPredictionMetrics,
-                              NodeEdgeEmbeddingPrediction, RemoveRandomConnections,
+                              GetPersonalizedClassifiers,
+                              NodeEdgeEmbeddingPrediction,
+                              PersonalizedClassifierPrediction,
+                              PersonalizedEdgeClassifierPrediction,
+                              PersonalizedNodeClassifierPrediction,
+                              RemoveRandomConnections,
                               RunLinkPredictionExperiment, SampleMissingConnections)
 from .embedding import (COMBINATION_OPTIONS, DEBUG_SUMMARY_OPTIONS,
                         EMBEDDING_OPTIONS, CombineEmbeddings, Embed,
@@ -65,5 +70,7 @@ __all__ = [
     "CombineEmbeddingsViaNodeEdgeClassifier", "EXPERIMENT_OPTIONS",
     "CalculateCommunityPredictionMetrics", "NodeEdgeEmbeddingPrediction",
     "RemoveRandomConnections", "RunLinkPredictionExperiment",
-    "SampleMissingConnections",
+    "SampleMissingConnections", "GetPersonalizedClassifiers",
+    "PersonalizedClassifierPrediction", "PersonalizedEdgeClassifierPrediction",
+    "PersonalizedNodeClassifierPrediction",
 ]

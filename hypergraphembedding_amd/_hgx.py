@@ -140,6 +140,14 @@ SIGNATURES = {
                            _pint]),
     "hgx_mlp_predict": (_int, [_vp, _int, _i64, _vp, _vp, _vp]),
     "hgx_mlp_last_stats": (_int, [_vp, _pdbl, _pi64, _pi64, _pdbl]),
+    "hgx_svc_create": (_int, [_vp, _int, _i64, _vp, ctypes.POINTER(_vp)]),
+    "hgx_svc_destroy": (_int, [_vp]),
+    "hgx_svc_fit": (_int, [_vp, _i64, _vp, _vp, _vp, _f32, _f32, _f32, _int,
+                           _vp, _vp]),
+    "hgx_svc_decision": (_int, [_vp, _i64, _vp, _vp, _vp]),
+    "hgx_svc_decision_vec": (_int, [_vp, _i64, _vp, _vp, _vp]),
+    "hgx_svc_get": (_int, [_vp, _vp, _vp]),
+    "hgx_svc_last_stats": (_int, [_vp, _pdbl, _pdbl]),
     "hgx_pyrandom_sample_missing": (_int, [_vp, _i32, _i32, _vp, _vp, _i64,
                                            _vp, _vp, _pi64]),
     "hgx_pyrandom_remove_connections": (_int, [_vp, _i64, _vp, _vp, _vp, _vp,
@@ -253,7 +261,7 @@ class Context:
     sample_mode3, sample_mode3_shift, sample_mode3_shift_e, train_fused,
     train_lanes, train_tb, train_prep_overlap, train_prep_cus, alg_long,
     alg_ks, alg_push, mlp_fuse_head, mlp_prefetch, mlp_wgrad_split,
-    stream_cus."""
+    svc_lds_m, stream_cus."""
     self._chk(lib().hgx_set_tuning(self.h, key.encode(), int(value)))
 
   # ---- incidence ----
@@ -739,6 +747,81 @@ class Mlp:
                                            ctypes.byref(fl)))
     return {"ms": ms.value, "samples": sm.value, "batches": bt.value,
             "flops": fl.value}
+
+
+class Svc:
+  """One hgx_svc engine (include/hgx.h, batched RBF C-SVC section): a float32
+  table on a Context, the problems of the last ``fit`` and their dual
+  coefficients on the device."""
+
+  def __init__(self, ctx, table):
+    tab = _c(table, np.float32)
+    assert tab.ndim == 2
+    self.ctx, self.dim, self.n_rows = ctx, tab.shape[1], tab.shape[0]
+    h = _vp()
+    ctx._chk(lib().hgx_svc_create(ctx.h, self.dim, self.n_rows, _ptr(tab),
+                                  ctypes.byref(h)))
+    self.h = h
+    self.n_prob = self.n_samp = 0
+    ctx._engines.add(self)
+
+  def close(self):
+    if getattr(self, "h", None):
+      lib().hgx_svc_destroy(self.h)
+      self.h = None
+
+  def __del__(self):
+    try:
+      self.close()
+    except Exception:
+      pass
+
+  def fit(self, off, row, label, C=1.0, gamma=0.1, eps=1e-3, max_iter=0):
+    """Solve the problems [off[p], off[p + 1]) of (row, 0/1 label) samples;
+    returns (iterations, status) per problem, status 1 = iteration cap."""
+    off, row = _c(off, np.int64), _c(row, np.int32)
+    label = _c(label, np.uint8)
+    n_prob = off.size - 1
+    assert n_prob >= 1 and row.size == label.size == off[-1]
+    iters = np.zeros(n_prob, np.int32)
+    status = np.zeros(n_prob, np.int32)
+    self.ctx._chk(lib().hgx_svc_fit(self.h, n_prob, _ptr(off), _ptr(row),
+                                    _ptr(label), C, gamma, eps, int(max_iter),
+                                    _ptr(iters), _ptr(status)))
+    self.n_prob, self.n_samp = n_prob, int(off[-1])
+    return iters, status
+
+  def decision(self, prob, row):
+    """f of table row ``row[q]`` under problem ``prob[q]``'s classifier."""
+    prob, row = _c(prob, np.int32), _c(row, np.int32)
+    assert prob.shape == row.shape
+    out = np.empty(prob.size, np.float32)
+    self.ctx._chk(lib().hgx_svc_decision(self.h, prob.size, _ptr(prob),
+                                         _ptr(row), _ptr(out)))
+    return out
+
+  def decision_vec(self, prob, vecs):
+    """f of the free vector ``vecs[q]`` under problem ``prob[q]``."""
+    prob = _c(prob, np.int32)
+    vecs = _c(vecs, np.float32).reshape(-1, self.dim)
+    assert prob.size == vecs.shape[0]
+    out = np.empty(prob.size, np.float32)
+    self.ctx._chk(lib().hgx_svc_decision_vec(self.h, prob.size, _ptr(prob),
+                                             _ptr(vecs), _ptr(out)))
+    return out
+
+  def get(self):
+    """(coef = s * alpha per sample, rho per problem) of the last fit."""
+    coef = np.empty(self.n_samp, np.float32)
+    rho = np.empty(self.n_prob, np.float32)
+    self.ctx._chk(lib().hgx_svc_get(self.h, _ptr(coef), _ptr(rho)))
+    return coef, rho
+
+  def stats(self):
+    f, d = ctypes.c_double(), ctypes.c_double()
+    self.ctx._chk(lib().hgx_svc_last_stats(self.h, ctypes.byref(f),
+                                           ctypes.byref(d)))
+    return {"fit_ms": f.value, "decision_ms": d.value}
 
 
 # ---- host utilities (no context, no device) --------------------------------

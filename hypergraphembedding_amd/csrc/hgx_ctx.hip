@@ -154,6 +154,10 @@ extern "C" int hgx_set_tuning(hgx_ctx *ctx, const char *key, int64_t value) {
   } else if (k == "mlp_wgrad_split") {
     HGX_CHECK(ctx, value >= 0 && value <= 1, HGX_EINVAL, "mlp_wgrad_split must be 0 or 1");
     t.mlp_wgrad_split = (int)value;
+  } else if (k == "svc_lds_m") {
+    HGX_CHECK(ctx, value == 64 || value == 128 || value == 192, HGX_EINVAL,
+              "svc_lds_m must be 64, 128 or 192");
+    t.svc_lds_m = (int)value;
   } else if (k == "train_prep_overlap") {
     HGX_CHECK(ctx, value >= 0 && value <= 2, HGX_EINVAL, "train_prep_overlap must be 0, 1 or 2");
     t.train_prep_overlap = (int)value;

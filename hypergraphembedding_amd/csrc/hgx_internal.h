@@ -85,6 +85,12 @@ struct Tuning {
   // that many CUs for the preparation
   int train_prep_overlap = 0;
   int train_prep_cus = 0;
+  // batched SVC: the largest problem whose kernel matrix is kept in LDS by
+  // the one-workgroup-per-problem solver (128: 64 KiB, two workgroups per
+  // CU; 192: 144 KiB, one per CU; 64: none, the one-wave solvers end
+  // there); larger problems recompute two kernel columns per iteration.
+  // The columns are bitwise the same either way.
+  int svc_lds_m = 128;
 };
 
 struct hgx_ctx {

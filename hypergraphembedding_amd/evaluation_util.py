@@ -14,9 +14,20 @@ Python's global ``random`` exactly as the reference's loops do: the state goes
 in, the same picks come out and the advanced state is put back, so
 ``random.seed(s)`` reproduces the reference's removals and negatives. The
 classifier trains on the MI355X dense-MLP engine (dense_mlp.py) reading the
-embedding rows in place. The per-edge / per-node SVC experiments
-(LP_EDGE_CLASSIFIERS / LP_NODE_CLASSIFIERS, 213-468) are outside the
-FOBE/HOBE path and raise.
+embedding rows in place.
+
+The per-edge / per-node SVC experiments (LP_EDGE_CLASSIFIERS /
+LP_NODE_CLASSIFIERS, 286-449 and 560-581) run on the device as well: one
+``SVC(C=1, gamma=0.1)`` per edge (node) that occurs in the candidate links,
+all of them solved in one batched launch (libhgx, csrc/hgx_svc.hip: libsvm's
+SMO in float32) and every candidate link scored in a second one. Kept
+surface: GetPersonalizedClassifiers, PersonalizedClassifierPrediction,
+PersonalizedEdgeClassifierPrediction, PersonalizedNodeClassifierPrediction,
+LetNothingIn, LetEverythingIn. The negatives of a classifier are drawn on the
+host (PersonalizedClassifierProblems): by default from a numpy generator
+seeded from Python's global ``random`` (the reference's distribution, not its
+picks), with ``rng="python"`` by the reference's own ``random.sample``
+expression.
 """
 
 import logging
@@ -29,6 +40,7 @@ from . import _hgx
 from .dense_mlp import LP_CLASSIFIER, DenseModel
 from .hypergraph_util import RemoveNodeFromEdge
 from .proto import EvaluationMetrics, ExperimentalResult, Hypergraph
+from .runtime import get_context
 
 log = logging.getLogger()
 
@@ -274,14 +286,259 @@ def NodeEdgeEmbeddingPrediction(hypergraph, embedding, potential_links,
           if np.asarray(s).reshape(-1)[0] > 0.5]
 
 
-def _personalized_not_supported(hypergraph, embedding, links,
-                                run_in_parallel=False):
-  raise RuntimeError("personalized SVC link prediction (evaluation_util.py:"
-                     "213-468) is outside the MI355X FOBE/HOBE path")
+################################################################################
+# Personalized classifiers: one RBF C-SVC per edge / per node (286-449)        #
+################################################################################
+
+SVC_C, SVC_GAMMA, SVC_EPS = 1.0, 0.1, 1e-3  # SVC(C=1, gamma=0.1), default tol
+PERSONALIZED_RNG_MODES = (None, "python")
+
+PersonalizedProblems = namedtuple(
+    "PersonalizedProblems",
+    ("off", "row", "label", "trained", "nothing", "everything"))
 
 
-PersonalizedEdgeClassifierPrediction = _personalized_not_supported
-PersonalizedNodeClassifierPrediction = _personalized_not_supported
+class LetEverythingIn:
+  """evaluation_util.py:286-289: the classifier of an index whose neighbours
+  are the whole table (one prediction per vector, like a fitted SVC)."""
+
+  def predict(self, vectors=(), *args, **kargs):
+    return np.ones(len(vectors), np.int64)
+
+  def decision_function(self, vectors=()):
+    return np.full(len(vectors), np.inf, np.float32)
+
+
+class LetNothingIn:
+  """evaluation_util.py:292-295: the classifier of an index with no
+  neighbours."""
+
+  def predict(self, vectors=(), *args, **kargs):
+    return np.zeros(len(vectors), np.int64)
+
+  def decision_function(self, vectors=()):
+    return np.full(len(vectors), -np.inf, np.float32)
+
+
+class PersonalizedClassifier:
+  """One trained classifier of a batch (problem ``prob`` of ``engine``).
+  ``decision_function`` scores free vectors on the device with the kernel
+  that scores table rows; ``predict`` is 1 where it is positive."""
+
+  def __init__(self, engine, prob):
+    self.engine, self.prob = engine, prob
+
+  def decision_function(self, vectors):
+    x = np.asarray(vectors, np.float32).reshape(-1, self.engine.dim)
+    if len(x) == 0:
+      return np.zeros(0, np.float32)
+    return self.engine.decision_vec(np.full(len(x), self.prob, np.int32), x)
+
+  def predict(self, vectors):
+    return (self.decision_function(vectors) > 0).astype(np.int64)
+
+
+def _draw_rows_without(gen, n_rows, taken, mark, k):
+  """k distinct rows of range(n_rows) outside `taken`, uniformly without
+  replacement, from the numpy generator `gen`. `mark` is a caller-owned
+  all-False scratch of n_rows bools (left all False)."""
+  free = n_rows - len(taken)
+  mark[taken] = True
+  if 2 * k > free:  # dense: permute the complement
+    rest = np.flatnonzero(~mark)
+    out = rest if k >= free else gen.choice(rest, k, replace=False)
+  else:  # sparse: rejection, first occurrences in draw order
+    out = np.empty(k, np.int64)
+    got = 0
+    while got < k:
+      cand = gen.integers(0, n_rows, 2 * (k - got) + 8)
+      cand = cand[~mark[cand]]
+      _, first = np.unique(cand, return_index=True)
+      cand = cand[np.sort(first)][:k - got]
+      mark[cand] = True
+      out[got:got + len(cand)] = cand
+      got += len(cand)
+    mark[out] = False
+  mark[taken] = False
+  return out
+
+
+def PersonalizedClassifierProblems(idx2neighbors, neighbor_row, idx_subset,
+                                   rng=None):
+  """The training problems of _train_personalized_classifier
+  (evaluation_util.py:318-352) for every idx of `idx_subset`, as rows of the
+  neighbour table: ``neighbor_row`` maps a neighbour's idx to its row (in the
+  order of the embedding map). Host only. Returns PersonalizedProblems:
+  problem p is samples [off[p], off[p + 1]) of (row, label) and belongs to
+  ``trained[p]``; positives (label 1) are the idx's neighbours, negatives
+  min(#non-neighbours, 2 * #neighbours) non-neighbours. ``nothing`` /
+  ``everything`` list the indices without neighbours / without
+  non-neighbours, which get no problem. An idx missing from `idx2neighbors`
+  and a neighbour missing from `neighbor_row` raise KeyError.
+
+  rng=None: one 62-bit seed is taken from Python's global ``random``
+  (``random.getrandbits(62)``, so ``random.seed(s)`` fixes the run) and the
+  negatives come from a numpy generator seeded with it, uniformly without
+  replacement per classifier: the reference's distribution, not its picks
+  (it calls ``random.sample`` on a set, whose order is the interpreter's hash
+  layout and which Python >= 3.11 rejects).
+  rng="python": the reference's expression itself on a tuple of that set,
+  ``random.sample(tuple(neighbor_row.keys() - pos_indices), k)``, per idx in
+  `idx_subset` order: the same picks and the same final ``random`` state as
+  the reference on the same interpreter.
+
+  The reference then permutes each problem's samples with
+  ``sklearn.utils.shuffle`` (:351). That only changes the order libsvm sees
+  them in, which moves the solution by less than its tolerance; it is not
+  reproduced and numpy's global state is not advanced."""
+  if rng not in PERSONALIZED_RNG_MODES:
+    raise ValueError("rng must be None or 'python', not %r" % (rng,))
+  n_rows = len(neighbor_row)
+  gen = mark = None
+  if rng is None:
+    gen = np.random.default_rng(random.getrandbits(62))
+    mark = np.zeros(n_rows, bool)
+  off, rows, labels = [0], [], []
+  trained, nothing, everything = [], [], []
+  for idx in idx_subset:
+    pos_indices = set(idx2neighbors[idx])
+    if len(pos_indices) == 0:
+      nothing.append(idx)
+      continue
+    if rng == "python":
+      neg_set = neighbor_row.keys() - pos_indices
+      num_neg = len(neg_set)
+    else:
+      num_neg = n_rows - sum(n in neighbor_row for n in pos_indices)
+    if num_neg == 0:
+      everything.append(idx)
+      continue
+    k = min(num_neg, len(pos_indices) * 2)
+    pos = np.fromiter((neighbor_row[n] for n in pos_indices), np.int64,
+                      len(pos_indices))
+    if rng == "python":
+      neg_indices = random.sample(tuple(neg_set), k)
+      neg = np.fromiter((neighbor_row[n] for n in neg_indices), np.int64, k)
+    else:
+      neg = _draw_rows_without(gen, n_rows, pos, mark, k)
+    rows += [pos, neg]
+    labels += [np.ones(len(pos), np.uint8), np.zeros(k, np.uint8)]
+    off.append(off[-1] + len(pos) + k)
+    trained.append(idx)
+  cat = lambda parts, dt: (np.concatenate(parts).astype(dt) if parts else
+                           np.zeros(0, dt))
+  return PersonalizedProblems(np.array(off, np.int64), cat(rows, np.int32),
+                              cat(labels, np.uint8), trained, nothing,
+                              everything)
+
+
+def _neighbor_table(embedding, per_edge):
+  """(idx -> row, rows x dim float32) of the table the classifiers read:
+  node embeddings for per-edge classifiers, edge embeddings per node."""
+  emb = embedding.node if per_edge else embedding.edge
+  row = {idx: i for i, idx in enumerate(emb)}
+  tab = np.zeros((len(row), embedding.dim), np.float32)
+  for idx, i in row.items():
+    tab[i] = emb[idx].values
+  return row, tab
+
+
+def _TrainPersonalizedClassifiers(hypergraph, embedding, per_edge, idx_subset,
+                                  rng):
+  """(engine or None, problems, idx -> problem, idx -> table row)."""
+  if per_edge:
+    idx2neighbors = {idx: edge.nodes for idx, edge in hypergraph.edge.items()}
+  else:
+    idx2neighbors = {idx: node.edges for idx, node in hypergraph.node.items()}
+  log.info("Training classifier per %s", "edge" if per_edge else "node")
+  if idx_subset is None:
+    idx_subset = idx2neighbors.keys()
+  else:
+    log.info("Subset provided with %i entires", len(idx_subset))
+  row, tab = _neighbor_table(embedding, per_edge)
+  problems = PersonalizedClassifierProblems(idx2neighbors, row, idx_subset,
+                                            rng=rng)
+  engine = None
+  if problems.trained:
+    engine = _hgx.Svc(get_context(), tab)
+    _, status = engine.fit(problems.off, problems.row, problems.label,
+                           C=SVC_C, gamma=SVC_GAMMA, eps=SVC_EPS)
+    capped = int(np.count_nonzero(status))
+    if capped:
+      log.warning("%i of %i personalized classifiers stopped at the "
+                  "iteration cap before converging", capped, len(status))
+  return engine, problems, {idx: p for p, idx in enumerate(problems.trained)}, row
+
+
+def GetPersonalizedClassifiers(hypergraph, embedding, per_edge=True,
+                               idx_subset=None, disable_pbar=False, rng=None):
+  """evaluation_util.py:355-386: a dict from idx to classifier, one per edge
+  (node embedding -> 0 / 1) or one per node (edge embedding -> 0 / 1), all
+  trained in one device launch. A classifier has ``predict(vectors)`` and
+  ``decision_function(vectors)``. `rng`: PersonalizedClassifierProblems."""
+  del disable_pbar
+  engine, problems, prob_of, _ = _TrainPersonalizedClassifiers(
+      hypergraph, embedding, per_edge, idx_subset, rng)
+  result = {idx: PersonalizedClassifier(engine, p)
+            for idx, p in prob_of.items()}
+  result.update((idx, LetNothingIn()) for idx in problems.nothing)
+  result.update((idx, LetEverythingIn()) for idx in problems.everything)
+  return result
+
+
+def PersonalizedClassifierPrediction(hypergraph, embedding, links,
+                                     per_edge=True, run_in_parallel=True,
+                                     disable_pbar=False, rng=None):
+  """evaluation_util.py:389-449: the candidate (node, edge) links that the
+  edge's (per_edge) or the node's classifier lets in. Links whose node or
+  edge has no embedding are dropped, only the classifiers the rest needs are
+  trained, and every remaining link is scored in place (rows of the
+  embedding table) in one device call; a link is predicted when its decision
+  value is positive. run_in_parallel and disable_pbar are accepted for
+  signature compatibility. `rng`: PersonalizedClassifierProblems."""
+  del run_in_parallel, disable_pbar
+  assert embedding.dim > 0
+  log.info("Removing potential links that do not have embeddings")
+  entity_idx_classifier_idx = [(n, e) if per_edge else (e, n)
+                               for n, e in links
+                               if n in embedding.node and e in embedding.edge]
+  necessary_classifiers = set(c for _, c in entity_idx_classifier_idx)
+  engine, problems, prob_of, row = _TrainPersonalizedClassifiers(
+      hypergraph, embedding, per_edge, necessary_classifiers, rng)
+  everything = set(problems.everything)
+  log.info("Running each classifier")
+  scored = [(k, prob_of[c], row[ent])
+            for k, (ent, c) in enumerate(entity_idx_classifier_idx)
+            if c in prob_of]
+  let_in = [c in everything for _, c in entity_idx_classifier_idx]
+  if scored:
+    f = engine.decision(np.array([p for _, p, _ in scored], np.int32),
+                        np.array([r for _, _, r in scored], np.int32))
+    for (k, _, _), v in zip(scored, f):
+      let_in[k] = bool(v > 0)
+  if engine is not None:
+    engine.close()
+  return [((ent, c) if per_edge else (c, ent))
+          for (ent, c), ok in zip(entity_idx_classifier_idx, let_in) if ok]
+
+
+def PersonalizedEdgeClassifierPrediction(hypergraph, embedding, links,
+                                         run_in_parallel=False, rng=None):
+  """evaluation_util.py:560-569."""
+  return PersonalizedClassifierPrediction(hypergraph, embedding, links,
+                                          per_edge=True,
+                                          run_in_parallel=run_in_parallel,
+                                          rng=rng)
+
+
+def PersonalizedNodeClassifierPrediction(hypergraph, embedding, links,
+                                         run_in_parallel=False, rng=None):
+  """evaluation_util.py:572-581."""
+  return PersonalizedClassifierPrediction(hypergraph, embedding, links,
+                                          per_edge=False,
+                                          run_in_parallel=run_in_parallel,
+                                          rng=rng)
+
 
 EXPERIMENT_OPTIONS = {
     "LP_EDGE_CLASSIFIERS": PersonalizedEdgeClassifierPrediction,

@@ -96,6 +96,11 @@ int hgx_mem_info(hgx_ctx *ctx, int64_t *free_bytes, int64_t *total_bytes);
  *   "mlp_wgrad_split"  combiner MLP training: 0 every weight gradient in one
  *                      launch (default), 1 two launches (the layers after the
  *                      pre layers, then the pre layers; measured slower)
+ *   "svc_lds_m"        batched SVC: largest problem (samples) solved with its
+ *                      kernel matrix in LDS, 128 (default, two workgroups per
+ *                      CU), 192 (one per CU) or 64 (only the one-wave
+ *                      solvers keep one); larger ones recompute two kernel
+ *                      columns per iteration (bit-identical results)
  *   "train_prep_overlap" trainer: 1 prepare chunk c + 1 (train_prep /
  *                      train_place) on a second stream while chunk c trains,
  *                      0 in line before each chunk (default); the same
@@ -477,6 +482,40 @@ int hgx_mlp_predict(hgx_mlp *m, int output, int64_t n, const int32_t *node_row,
  * gradients of the unpadded layers). */
 int hgx_mlp_last_stats(const hgx_mlp *m, double *ms, int64_t *samples,
                        int64_t *batches, double *flops);
+
+/* ---- batched RBF C-SVC (per-edge / per-node link-prediction classifiers) *
+ * Replaces the sklearn.svm.SVC(C=1, gamma=0.1) fits and predictions of
+ * _train_personalized_classifier / PersonalizedClassifierPrediction
+ * (evaluation_util.py:318-449): many small independent dual problems per
+ * launch, libsvm's SMO (second-order working-set selection, stop at
+ * m(alpha) - M(alpha) < eps) in float32, K(x, y) = exp(-gamma |x - y|^2).
+ * A problem p is the samples [off[p], off[p + 1]): a row of the table and a
+ * 0 / 1 label each; there is no limit on a problem's size. Label 1 is the
+ * positive side of the decision value f = sum_j coef_j K(x_j, q) - rho,
+ * coef = +-alpha. The dual coefficients and rho stay on the device
+ * (hgx_svc_get copies them out, coef in sample order). max_iter <= 0 means
+ * max(10000, 100 m) iterations per problem; a problem that reaches the cap
+ * gets status 1 (0: converged) and keeps its current alpha and rho.
+ * HGX_EVALUE before any launch: a non-finite table or query value, a row or
+ * problem index out of range, a label other than 0 / 1, a problem without
+ * samples or with one class only, C, gamma or eps not positive.
+ * hgx_svc_decision scores rows of the table, hgx_svc_decision_vec host
+ * vectors (n_q x dim), with the same kernel. hgx_svc_last_stats: device
+ * time (ms, HIP events over the launches) of the last fit and decision. */
+typedef struct hgx_svc hgx_svc;
+int hgx_svc_create(hgx_ctx *ctx, int dim, int64_t n_rows, const float *rows,
+                   hgx_svc **out);
+int hgx_svc_destroy(hgx_svc *s);
+int hgx_svc_fit(hgx_svc *s, int64_t n_prob, const int64_t *off,
+                const int32_t *row, const uint8_t *label, float C, float gamma,
+                float eps, int max_iter, int32_t *iters_out,
+                int32_t *status_out);
+int hgx_svc_decision(hgx_svc *s, int64_t n_q, const int32_t *prob,
+                     const int32_t *row, float *f_out);
+int hgx_svc_decision_vec(hgx_svc *s, int64_t n_q, const int32_t *prob,
+                         const float *vecs, float *f_out);
+int hgx_svc_get(hgx_svc *s, float *coef_out, float *rho_out);
+int hgx_svc_last_stats(const hgx_svc *s, double *fit_ms, double *decision_ms);
 
 /* ---- host utilities (bench / test data; not reference entry points) --- *
  * Power-law synthetic incidence of SURVEY.md §8(d) (C4/C5): node degree
