@@ -42,6 +42,7 @@ from .embedding import (COMBINATION_OPTIONS, DEBUG_SUMMARY_OPTIONS,
                         EMBEDDING_OPTIONS, CombineEmbeddings, Embed,
                         EmbedHg2vAdjJaccard, EmbedHg2vAlgDist, EmbedHg2vBoolean,
                         EmbedHg2vNeighborhoodWeightedJaccard)
+from .svd import EmbedRandom, EmbedSvd, svd_incidence
 
 __all__ = [
     # proto
@@ -52,6 +53,8 @@ __all__ = [
     "COMBINATION_OPTIONS", "CombineEmbeddings", "EmbedHg2vBoolean",
     "EmbedHg2vAlgDist", "EmbedAlgebraicDistance", "EmbedHg2vAdjJaccard",
     "EmbedHg2vNeighborhoodWeightedJaccard", "WeightedJaccardSamples",
+    # comparison baselines (reference embedding.py:110-140)
+    "EmbedSvd", "EmbedRandom", "svd_incidence",
     # hot-path pieces
     "BooleanSamples", "AlgebraicDistanceSamples", "SamplesToModelInput",
     "SimilarityRecord", "UniformWeight", "WeightByNeighborhood",

@@ -148,6 +148,18 @@ SIGNATURES = {
     "hgx_svc_decision_vec": (_int, [_vp, _i64, _vp, _vp, _vp]),
     "hgx_svc_get": (_int, [_vp, _vp, _vp]),
     "hgx_svc_last_stats": (_int, [_vp, _pdbl, _pdbl]),
+    "hgx_svd_create": (_int, [_vp, _int, ctypes.POINTER(_vp)]),
+    "hgx_svd_destroy": (_int, [_vp]),
+    "hgx_svd_panel": (_int, [_vp, _int, _int, _int]),
+    "hgx_svd_set": (_int, [_vp, _int, _int, _int, _vp]),
+    "hgx_svd_get": (_int, [_vp, _int, _int, _int, _vp]),
+    "hgx_svd_copy": (_int, [_vp, _int, _int, _int, _int, _int]),
+    "hgx_svd_spmm": (_int, [_vp, _int, _int, _int, _int, _int]),
+    "hgx_svd_gram": (_int, [_vp, _int, _int, _int, _int, _int, _int, _vp]),
+    "hgx_svd_apply": (_int, [_vp, _int, _int, _int, _int, _int, _int, _vp,
+                             ctypes.c_double]),
+    "hgx_svd_scale": (_int, [_vp, _int, _int, _int, _vp]),
+    "hgx_svd_last_stats": (_int, [_vp, _pdbl, _pdbl, _pi64, _pi64, _pi64]),
     "hgx_pyrandom_sample_missing": (_int, [_vp, _i32, _i32, _vp, _vp, _i64,
                                            _vp, _vp, _pi64]),
     "hgx_pyrandom_remove_connections": (_int, [_vp, _i64, _vp, _vp, _vp, _vp,
@@ -822,6 +834,83 @@ class Svc:
     self.ctx._chk(lib().hgx_svc_last_stats(self.h, ctypes.byref(f),
                                            ctypes.byref(d)))
     return {"fit_ms": f.value, "decision_ms": d.value}
+
+
+class Svd:
+  """One hgx_svd engine (include/hgx.h, truncated-SVD block primitives) on a
+  Context whose incidence is uploaded: fp32 panels with one row per edge
+  (side 0) or per node (side 1) in slots 0..7, and the block products on
+  column ranges of them. This is the device backend of svd.svd_incidence."""
+
+  EDGE, NODE = 0, 1
+
+  def __init__(self, ctx, long_row=0):
+    self.ctx = ctx
+    h = _vp()
+    ctx._chk(lib().hgx_svd_create(ctx.h, int(long_row), ctypes.byref(h)))
+    self.h = h
+    self.rows = (ctx.inc.E, ctx.inc.N)
+    self._side = {}
+    ctx._engines.add(self)
+
+  def close(self):
+    if getattr(self, "h", None):
+      lib().hgx_svd_destroy(self.h)
+      self.h = None
+
+  def __del__(self):
+    try:
+      self.close()
+    except Exception:
+      pass
+
+  def panel(self, slot, side, width):
+    self.ctx._chk(lib().hgx_svd_panel(self.h, slot, side, width))
+    self._side[slot] = side
+
+  def set(self, slot, col0, host):
+    host = _c(host, np.float32)
+    assert host.ndim == 2 and host.shape[0] == self.rows[self._side[slot]]
+    self.ctx._chk(lib().hgx_svd_set(self.h, slot, col0, host.shape[1],
+                                    _ptr(host)))
+
+  def get(self, slot, col0, ncols):
+    out = np.empty((self.rows[self._side[slot]], ncols), np.float32)
+    self.ctx._chk(lib().hgx_svd_get(self.h, slot, col0, ncols, _ptr(out)))
+    return out
+
+  def copy(self, dst, dcol0, src, scol0, ncols):
+    self.ctx._chk(lib().hgx_svd_copy(self.h, dst, dcol0, src, scol0, ncols))
+
+  def spmm(self, dst, dcol0, src, scol0, ncols):
+    self.ctx._chk(lib().hgx_svd_spmm(self.h, dst, dcol0, src, scol0, ncols))
+
+  def gram(self, pslot, pcol0, p, qslot, qcol0, q):
+    out = np.empty((p, q), np.float64)
+    self.ctx._chk(lib().hgx_svd_gram(self.h, pslot, pcol0, p, qslot, qcol0, q,
+                                     _ptr(out)))
+    return out
+
+  def apply(self, dst, dcol0, src, scol0, M, beta=0.0):
+    M = _c(M, np.float64)
+    assert M.ndim == 2
+    q, p = M.shape
+    self.ctx._chk(lib().hgx_svd_apply(self.h, dst, dcol0, p, src, scol0, q,
+                                      _ptr(M), float(beta)))
+
+  def scale(self, slot, col0, scale):
+    scale = _c(scale, np.float64).ravel()
+    self.ctx._chk(lib().hgx_svd_scale(self.h, slot, col0, scale.size,
+                                      _ptr(scale)))
+
+  def stats(self):
+    ms, by = ctypes.c_double(), ctypes.c_double()
+    n, c, d = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    self.ctx._chk(lib().hgx_svd_last_stats(self.h, ctypes.byref(ms),
+                                           ctypes.byref(by), ctypes.byref(n),
+                                           ctypes.byref(c), ctypes.byref(d)))
+    return {"spmm_ms": ms.value, "spmm_bytes": by.value, "spmm_calls": n.value,
+            "spmm_cols": c.value, "dense_calls": d.value}
 
 
 # ---- host utilities (no context, no device) --------------------------------

@@ -260,6 +260,7 @@ extern "C" int hgx_upload_incidence(hgx_ctx *ctx, int32_t N, int32_t E,
   HGX_TRY(check_csr(ctx, "node-major", N, E, nnz, rowptr_n, col_n));
   HGX_TRY(check_csr(ctx, "edge-major", E, N, nnz, rowptr_e, col_e));
   HGX_HIP(ctx, hipSetDevice(ctx->device));
+  ctx->inc_gen++;
   HGX_TRY(hgx_ensure(ctx, ctx->rp_n, sizeof(int32_t) * (N + 1)));
   HGX_TRY(hgx_ensure(ctx, ctx->rp_e, sizeof(int32_t) * (E + 1)));
   HGX_TRY(hgx_ensure(ctx, ctx->col_n, sizeof(int32_t) * (nnz + 1)));

@@ -102,6 +102,9 @@ struct hgx_ctx {
   // ---- incidence (compressed, both orientations, sorted columns) ----
   int32_t N = 0, E = 0;
   int64_t nnz = 0;
+  // counts the hgx_upload_incidence calls: an engine built on the resident
+  // incidence (hgx_svd) keeps the count it was created at
+  uint64_t inc_gen = 0;
   DevBuf rp_n, col_n, rp_e, col_e;
   // alg-dist row-blocks (<= 64 whole rows, <= 256 incidences each; a longer
   // row is a block of its own): row starts, nblk + 1 entries

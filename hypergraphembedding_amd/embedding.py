@@ -10,9 +10,11 @@ Registry and signatures kept for the FOBE/HOBE path: ``Embed(args, hg)``
 ``_hypergraph2vec_skeleton`` (269-305) runs entirely on one device context:
 incidence upload -> sampler -> records stay in HBM -> tables initialised on
 device -> Keras-semantics fit -> rows idx+1 copied into the proto.
-The reference's other methods (SVD, NMF, node2vec, auto-encoder) are
-outside this hot path: their keys raise like the reference's
-``method_not_supported`` (419-420).
+``EmbedRandom`` and ``EmbedSvd`` (110-140) live in svd.py; "RANDOM" is
+registered, "SVD" is bound by the integrator. The
+reference's other methods (NMF, node2vec, auto-encoder) are outside this
+hot path: their keys raise like the reference's ``method_not_supported``
+(419-420).
 """
 
 import logging
@@ -29,6 +31,7 @@ from .hg2v_sample import (_quotas, row_class_quota, sample_fobe, sample_hobe,
 from .hypergraph_util import Incidence
 from .proto import HypergraphEmbedding
 from .runtime import check_rng, get_context, numpy_seed, numpy_state_seed
+from .svd import EmbedRandom, EmbedSvd
 
 log = logging.getLogger()
 
@@ -571,9 +574,11 @@ EMBEDDING_OPTIONS = {
     "HG2V_ALG_DIST": EmbedHg2vAlgDist,
     "HG2V_BOOLEAN_NS": lambda h, d, **kw: EmbedHg2vBoolean(h, d, neg_samples=500,
                                                            **kw),
-    # outside the FOBE/HOBE hot path (SURVEY §2 "OUT OF SCOPE")
+    # outside the FOBE/HOBE hot path (SURVEY §2 "OUT OF SCOPE"). EmbedSvd
+    # exists (svd.py); a reference-side integrator binds "SVD" to it
+    # (INTEGRATION.md §1), this registry keeps the key unsupported
     "SVD": method_not_supported,
-    "RANDOM": method_not_supported,
+    "RANDOM": EmbedRandom,
     "NMF": method_not_supported,
     "AUTO_ENCODER": method_not_supported,
     "N2V3_BIPARTIDE": method_not_supported,
@@ -597,4 +602,5 @@ __all__ = ["Embed", "EMBEDDING_OPTIONS", "DEBUG_SUMMARY_OPTIONS",
            "COMBINATION_OPTIONS", "CombineEmbeddings", "EmbedHg2vBoolean",
            "EmbedHg2vAlgDist", "EmbedAlgebraicDistance", "EmbedHg2vAdjJaccard",
            "EmbedHg2vNeighborhoodWeightedJaccard",
-           "CombineEmbeddingsViaConcatenation", "method_not_supported"]
+           "CombineEmbeddingsViaConcatenation", "method_not_supported",
+           "EmbedSvd", "EmbedRandom"]

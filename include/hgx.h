@@ -517,6 +517,56 @@ int hgx_svc_decision_vec(hgx_svc *s, int64_t n_q, const int32_t *prob,
 int hgx_svc_get(hgx_svc *s, float *coef_out, float *rho_out);
 int hgx_svc_last_stats(const hgx_svc *s, double *fit_ms, double *decision_ms);
 
+/* ---- block primitives of the truncated SVD of the incidence -------------- *
+ * The device half of EmbedSvd (reference embedding.py:110-126, which calls
+ * scipy.sparse.linalg.svds): hypergraphembedding_amd/svd.py runs a
+ * thick-restart block Lanczos through these calls, and only small matrices
+ * (at most 1056 x 1056 float64) and the final vectors cross to the host.
+ * The engine works on the incidence uploaded by hgx_upload_incidence before
+ * hgx_svd_create (HGX_ESTATE without one, or after it was replaced).
+ * long_row: rows with more incidences are summed in pieces of that many
+ * (0: the library's default, 512); a result does not depend on anything
+ * else, and two calls with the same operands are bitwise equal.
+ *
+ * A panel slot (0..7) holds a row-major fp32 matrix with one row per edge
+ * (side 0) or per node (side 1); hgx_svd_panel (re)allocates it zeroed.
+ * Every call below works on the columns [col0, col0 + ncols) of a slot
+ * (HGX_EINVAL outside the panel):
+ *   hgx_svd_set / _get  host (rows x ncols, row-major) <-> device
+ *   hgx_svd_copy        dst <- src, same side, not overlapping
+ *   hgx_svd_spmm        dst <- A src (src on the edge side, dst on the node
+ *                       side) or dst <- A^T src (the other way round); a row
+ *                       is summed in CSR column order, an empty row is zero
+ *   hgx_svd_gram        out (p x q float64, row-major, host) <- P^T Q,
+ *                       accumulated in float64; p, q <= 1056 (HGX_EUNSUP)
+ *   hgx_svd_apply       dst (p columns) <- beta dst + src (q columns) M, M a
+ *                       q x p row-major float64 host matrix, accumulated in
+ *                       float64 and rounded once; dst and src must not share
+ *                       columns; p, q <= 1056
+ *   hgx_svd_scale       column j of the range <- column j * scale[j]
+ * A non-finite entry of M, beta or scale is HGX_EVALUE before any launch.
+ * hgx_svd_last_stats: device time (ms, HIP events) and algorithmic bytes
+ * (4 nnz + 4 b nnz + 4 b rows per product of b columns) summed over the
+ * products so far, their count and their total columns, and the count of
+ * dense calls (gram, apply, scale). */
+typedef struct hgx_svd hgx_svd;
+int hgx_svd_create(hgx_ctx *ctx, int long_row, hgx_svd **out);
+int hgx_svd_destroy(hgx_svd *s);
+int hgx_svd_panel(hgx_svd *s, int slot, int side, int width);
+int hgx_svd_set(hgx_svd *s, int slot, int col0, int ncols, const float *host);
+int hgx_svd_get(hgx_svd *s, int slot, int col0, int ncols, float *host);
+int hgx_svd_copy(hgx_svd *s, int dst, int dcol0, int src, int scol0, int ncols);
+int hgx_svd_spmm(hgx_svd *s, int dst, int dcol0, int src, int scol0, int ncols);
+int hgx_svd_gram(hgx_svd *s, int pslot, int pcol0, int p, int qslot, int qcol0,
+                 int q, double *out);
+int hgx_svd_apply(hgx_svd *s, int dst, int dcol0, int p, int src, int scol0,
+                  int q, const double *M, double beta);
+int hgx_svd_scale(hgx_svd *s, int slot, int col0, int ncols,
+                  const double *scale);
+int hgx_svd_last_stats(hgx_svd *s, double *spmm_ms, double *spmm_bytes,
+                       int64_t *spmm_calls, int64_t *spmm_cols,
+                       int64_t *dense_calls);
+
 /* ---- host utilities (bench / test data; not reference entry points) --- *
  * Power-law synthetic incidence of SURVEY.md §8(d) (C4/C5): node degree
  * 1 + Poisson(mean_degree - 1), distinct edges per node drawn with
