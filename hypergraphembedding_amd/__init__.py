@@ -43,6 +43,7 @@ from .embedding import (COMBINATION_OPTIONS, DEBUG_SUMMARY_OPTIONS,
                         EmbedHg2vAdjJaccard, EmbedHg2vAlgDist, EmbedHg2vBoolean,
                         EmbedHg2vNeighborhoodWeightedJaccard)
 from .svd import EmbedRandom, EmbedSvd, svd_incidence
+from .nmf import EmbedNMF, nmf_incidence
 
 __all__ = [
     # proto
@@ -53,8 +54,8 @@ __all__ = [
     "COMBINATION_OPTIONS", "CombineEmbeddings", "EmbedHg2vBoolean",
     "EmbedHg2vAlgDist", "EmbedAlgebraicDistance", "EmbedHg2vAdjJaccard",
     "EmbedHg2vNeighborhoodWeightedJaccard", "WeightedJaccardSamples",
-    # comparison baselines (reference embedding.py:110-140)
-    "EmbedSvd", "EmbedRandom", "svd_incidence",
+    # comparison baselines (reference embedding.py:110-162)
+    "EmbedSvd", "EmbedRandom", "svd_incidence", "EmbedNMF", "nmf_incidence",
     # hot-path pieces
     "BooleanSamples", "AlgebraicDistanceSamples", "SamplesToModelInput",
     "SimilarityRecord", "UniformWeight", "WeightByNeighborhood",

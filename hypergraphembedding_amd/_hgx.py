@@ -160,6 +160,10 @@ SIGNATURES = {
                              ctypes.c_double]),
     "hgx_svd_scale": (_int, [_vp, _int, _int, _int, _vp]),
     "hgx_svd_last_stats": (_int, [_vp, _pdbl, _pdbl, _pi64, _pi64, _pi64]),
+    "hgx_svd_cd_sweep": (_int, [_vp, _int, _int, _int, _int, _int, _vp, _pdbl]),
+    "hgx_svd_cd_sweep_fused": (_int, [_vp, _int, _int, _int, _int, _int, _vp,
+                                      _pdbl]),
+    "hgx_svd_cd_last_stats": (_int, [_vp, _pdbl, _pi64]),
     "hgx_pyrandom_sample_missing": (_int, [_vp, _i32, _i32, _vp, _vp, _i64,
                                            _vp, _vp, _pi64]),
     "hgx_pyrandom_remove_connections": (_int, [_vp, _i64, _vp, _vp, _vp, _vp,
@@ -911,6 +915,35 @@ class Svd:
                                            ctypes.byref(c), ctypes.byref(d)))
     return {"spmm_ms": ms.value, "spmm_bytes": by.value, "spmm_calls": n.value,
             "spmm_cols": c.value, "dense_calls": d.value}
+
+  def cd_sweep(self, pslot, pcol0, bslot, bcol0, Q):
+    """One coordinate-descent sweep (hgx_svd_cd_sweep) of the k columns from
+    pcol0 of pslot against the k columns from bcol0 of bslot, Q the k x k
+    float64 Gram of the other factor; returns the summed violation."""
+    Q = _c(Q, np.float64)
+    assert Q.ndim == 2 and Q.shape[0] == Q.shape[1]
+    v = ctypes.c_double()
+    self.ctx._chk(lib().hgx_svd_cd_sweep(self.h, pslot, pcol0, bslot, bcol0,
+                                         Q.shape[0], _ptr(Q), ctypes.byref(v)))
+    return v.value
+
+  def cd_sweep_fused(self, pslot, pcol0, xslot, xcol0, Q):
+    """cd_sweep with the product formed inside the kernel in float64 from the
+    k columns from xcol0 of xslot, a panel of the other side
+    (hgx_svd_cd_sweep_fused)."""
+    Q = _c(Q, np.float64)
+    assert Q.ndim == 2 and Q.shape[0] == Q.shape[1]
+    v = ctypes.c_double()
+    self.ctx._chk(lib().hgx_svd_cd_sweep_fused(
+        self.h, pslot, pcol0, xslot, xcol0, Q.shape[0], _ptr(Q),
+        ctypes.byref(v)))
+    return v.value
+
+  def cd_stats(self):
+    ms, n = ctypes.c_double(), ctypes.c_int64()
+    self.ctx._chk(lib().hgx_svd_cd_last_stats(self.h, ctypes.byref(ms),
+                                              ctypes.byref(n)))
+    return {"sweep_ms": ms.value, "sweeps": n.value}
 
 
 # ---- host utilities (no context, no device) --------------------------------

@@ -27,6 +27,8 @@
 //   apply  P = beta P + Q M with M a small float64 matrix from the host,
 //          accumulated in float64 and rounded once to fp32.
 //   scale  Y = Y diag(s).
+//   cd_sweep  one non-negative coordinate-descent sweep of the NMF solver
+//          (nmf.py) over the rows of a panel: see the kernel below.
 #include <algorithm>
 #include <cmath>
 
@@ -37,6 +39,10 @@ namespace {
 constexpr int kSlots = 8;
 constexpr int kMaxSmall = 1056;  // largest p, q of gram / apply
 constexpr int kTB = 256;
+constexpr int kCdTB = 1024;      // cd_sweep workgroup: 16 waves share one Q
+constexpr int kCdMaxR = 8;       // coordinates of a row per lane
+constexpr int kCdMaxK = 64 * kCdMaxR;  // the sweep's limit (include/hgx.h)
+constexpr size_t kCdLds = 160 * 1024;  // a CU's LDS
 
 struct Panel {
   DevBuf buf;
@@ -63,7 +69,12 @@ struct hgx_svd {
   SvdLong lg[2];  // [0]: edge rows (rp_e), [1]: node rows (rp_n)
   DevBuf part;    // long-row partial rows (float64)
   DevBuf gpart, gout, mdev;  // gram chunk partials / result, apply's M
+  DevBuf cdq, cdviol;        // cd_sweep: Q^T, per-row violations and their sum
   hipEvent_t e0 = nullptr, e1 = nullptr;
+  hipEvent_t c0 = nullptr, c1 = nullptr;  // around a cd_sweep
+  int ncu = 0;
+  double cd_ms = 0;
+  int64_t cd_sweeps = 0;
   bool spmm_pending = false;
   double spmm_pending_bytes = 0;
   double spmm_ms = 0, spmm_bytes = 0;
@@ -303,6 +314,169 @@ __global__ __launch_bounds__(kTB) void scale_cols(float *__restrict__ Y, int64_t
   Y[r * ld + c] = (float)((double)Y[r * ld + c] * s[c]);
 }
 
+// ---- cd_sweep --------------------------------------------------------------
+// One sweep of the coordinate-descent NMF solver (sklearn's
+// _update_cdnmf_fast, no regularisation, no shuffle) over the rows of the
+// n x k view P, with B the matching rows of the sparse product and Q the
+// k x k Gram of the other factor:
+//   for t = 0..k-1:  g = sum_r Q[t][r] P[i][r] - B[i][t]
+//                    viol += |P[i][t] == 0 ? min(g, 0) : g|
+//                    if Q[t][t] != 0: P[i][t] = fp32(max(P[i][t] - g / Q[t][t], 0))
+// all in float64, later coordinates seeing the rounded value.
+//
+// A group of G lanes (a power of two, k rounded up, at most 64) owns a row
+// and lane `sub` of it holds the coordinates r = j G + sub (j < R) with their
+// gradient entries g_r = (P_i Q - B_i)_r in float64 registers. The gradient
+// is built coordinate by coordinate (g += P[i][t] Q^T[t][:] for the non-zero
+// P[i][t]) and then kept up to date: step t's owner lane forms the new value
+// and the change delta, one 64-bit shuffle hands delta to the group, and
+// every lane adds delta Q^T[t][r] to its entries. A coordinate that stays
+// clamped at zero (delta = 0) costs no row of Q. There is no cross-lane sum
+// in the chain. QT is Q transposed, so that the entries a group reads at step
+// t are consecutive; with LDSQ it is staged once per workgroup in LDS (16
+// waves share it, consecutive float64 per lane: no bank conflict), above 160
+// KiB (k > 143) it is read through L2. The row's violation is summed over
+// the group by a fixed xor tree and written per row; cd_violation adds the
+// rows in a fixed order. Rows are handed out grid-stride, and nothing a row
+// computes depends on which group got it.
+//
+// Fused form (rp != nullptr): B is not read from a panel but formed here, row
+// i of A X (or A^T X) summed in CSR column order in float64 from the other
+// side's panel X (B, ldb then point at X), and never rounded to fp32. The
+// gradient of a badly scaled component cancels B against the Gram terms, and
+// there the fp32 rounding of a stored product is the solver's largest error
+// (DESIGN §4.8). A row is gathered by its own group, however long it is.
+template <int R, bool LDSQ>
+__global__ __launch_bounds__(kCdTB) void cd_sweep_rows(
+    float *__restrict__ P, int64_t ldp, const float *__restrict__ B, int64_t ldb, int k,
+    const double *__restrict__ QT, int64_t n, int G, double *__restrict__ viol,
+    const int32_t *__restrict__ rp, const int32_t *__restrict__ col) {
+  extern __shared__ __attribute__((aligned(16))) double cd_q[];
+  if (LDSQ) {
+    for (int i = threadIdx.x; i < k * k; i += kCdTB) cd_q[i] = QT[i];
+    __syncthreads();
+  }
+  auto qt = [&](int t, int r) -> double {
+    return LDSQ ? cd_q[t * k + r] : QT[(int64_t)t * k + r];
+  };
+  const int lane = threadIdx.x & 63, sub = lane & (G - 1);
+  const int rpw = 64 / G;
+  const int64_t wave = (int64_t)blockIdx.x * (kCdTB / 64) + (threadIdx.x >> 6);
+  const int64_t stride = (int64_t)gridDim.x * (kCdTB / 64) * rpw;
+  // a group leaves as a whole: the shuffles below read lanes of the own group
+  for (int64_t row = wave * rpw + lane / G; row < n; row += stride) {
+    float *p = P + row * ldp;
+    double g[R];
+    float pv[R];
+    if (rp) {
+#pragma unroll
+      for (int j = 0; j < R; j++) {
+        const int r = j * G + sub;
+        pv[j] = r < k ? p[r] : 0.f;
+        g[j] = 0.0;
+      }
+      const int beg = rp[row], end = rp[row + 1];
+      int e = beg;
+      for (; e + 2 <= end; e += 2) {  // two source rows in flight, added in order
+        const float *x0 = B + (int64_t)col[e] * ldb;
+        const float *x1 = B + (int64_t)col[e + 1] * ldb;
+        float a0[R], a1[R];
+#pragma unroll
+        for (int j = 0; j < R; j++) {
+          const int r = j * G + sub;
+          a0[j] = r < k ? x0[r] : 0.f;
+          a1[j] = r < k ? x1[r] : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < R; j++) g[j] = (g[j] - (double)a0[j]) - (double)a1[j];
+      }
+      if (e < end) {
+        const float *x0 = B + (int64_t)col[e] * ldb;
+#pragma unroll
+        for (int j = 0; j < R; j++) {
+          const int r = j * G + sub;
+          if (r < k) g[j] -= (double)x0[r];
+        }
+      }
+    } else {
+      const float *b = B + row * ldb;
+#pragma unroll
+      for (int j = 0; j < R; j++) {
+        const int r = j * G + sub;
+        pv[j] = r < k ? p[r] : 0.f;
+        g[j] = r < k ? -(double)b[r] : 0.0;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+      const int lim = min(G, k - j * G);
+      for (int l = 0; l < lim; l++) {
+        const float pt = __shfl(pv[j], l, G);
+        if (pt != 0.f) {
+          const int t = j * G + l;
+          const double d = pt;
+#pragma unroll
+          for (int jj = 0; jj < R; jj++) {
+            const int r = jj * G + sub;
+            if (r < k) g[jj] = fma(d, qt(t, r), g[jj]);
+          }
+        }
+      }
+    }
+    double v = 0.0;
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+      const int lim = min(G, k - j * G);
+      for (int l = 0; l < lim; l++) {
+        const int t = j * G + l;
+        double delta = 0.0;
+        if (sub == l) {
+          const double gt = g[j];
+          const float pt = pv[j];
+          v += fabs(pt == 0.f ? fmin(gt, 0.0) : gt);
+          const double qtt = qt(t, t);
+          if (qtt != 0.0) {
+            const float nw = (float)fmax((double)pt - gt / qtt, 0.0);
+            delta = (double)nw - (double)pt;
+            pv[j] = nw;
+          }
+        }
+        delta = __shfl(delta, l, G);
+        if (delta != 0.0) {
+#pragma unroll
+          for (int jj = 0; jj < R; jj++) {
+            const int r = jj * G + sub;
+            if (r < k) g[jj] = fma(delta, qt(t, r), g[jj]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+      const int r = j * G + sub;
+      if (r < k) p[r] = pv[j];
+    }
+    for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, G);
+    if (sub == 0) viol[row] = v;
+  }
+}
+
+// out[0] = the n per-row violations added in a fixed order: thread i adds the
+// rows i, i + 1024, ... in turn, then a tree over the threads
+__global__ __launch_bounds__(kCdTB) void cd_violation(const double *__restrict__ viol,
+                                                      int64_t n, double *__restrict__ out) {
+  __shared__ double red[kCdTB];
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += kCdTB) s += viol[i];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = kCdTB / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = red[0];
+}
+
 // ---- host side -------------------------------------------------------------
 int make_long(hgx_svd *s, const DevBuf &rp_dev, int32_t nrows, SvdLong &out) {
   hgx_ctx *ctx = s->ctx;
@@ -400,6 +574,28 @@ int launch_spmm(hgx_svd *s, int dside, const float *X, int64_t ldx, float *Y,
   return HGX_OK;
 }
 
+template <int R, bool LDSQ>
+int launch_cd(hgx_svd *s, float *P, int64_t ldp, const float *B, int64_t ldb, int k,
+              int64_t n, int G, const int32_t *rp, const int32_t *col) {
+  hgx_ctx *ctx = s->ctx;
+  const size_t lds = LDSQ ? sizeof(double) * (size_t)k * k : 0;
+  auto kern = cd_sweep_rows<R, LDSQ>;
+  if (lds > 64 * 1024)
+    HGX_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)lds));
+  // resident workgroups only (two of 1024 threads fit a CU when their LDS
+  // does): a workgroup stages Q once and walks its rows grid-stride
+  const int64_t per_block = (int64_t)(kCdTB / 64) * (64 / G);
+  const int64_t need = (n + per_block - 1) / per_block;
+  const int64_t cap = (int64_t)std::max(s->ncu, 1) * (lds <= kCdLds / 2 ? 2 : 1);
+  hipLaunchKernelGGL(kern, dim3((unsigned)std::min(need, cap)), dim3(kCdTB), lds,
+                     ctx->stream, P, ldp, B, ldb, k, s->cdq.as<double>(), n, G,
+                     s->cdviol.as<double>(), rp, col);
+  HGX_LAUNCH_CHECK(ctx);
+  return HGX_OK;
+}
+
 }  // namespace
 
 extern "C" int hgx_svd_create(hgx_ctx *ctx, int long_row, hgx_svd **out) {
@@ -421,6 +617,11 @@ extern "C" int hgx_svd_create(hgx_ctx *ctx, int long_row, hgx_svd **out) {
   if (!rc) rc = make_long(s, ctx->rp_n, ctx->N, s->lg[1]);
   if (!rc && hipEventCreate(&s->e0) != hipSuccess) rc = hgx_fail(ctx, HGX_EHIP, "event");
   if (!rc && hipEventCreate(&s->e1) != hipSuccess) rc = hgx_fail(ctx, HGX_EHIP, "event");
+  if (!rc && hipEventCreate(&s->c0) != hipSuccess) rc = hgx_fail(ctx, HGX_EHIP, "event");
+  if (!rc && hipEventCreate(&s->c1) != hipSuccess) rc = hgx_fail(ctx, HGX_EHIP, "event");
+  if (!rc && hipDeviceGetAttribute(&s->ncu, hipDeviceAttributeMultiprocessorCount,
+                                   ctx->device) != hipSuccess)
+    rc = hgx_fail(ctx, HGX_EHIP, "multiprocessor count");
   if (rc) {
     hgx_svd_destroy(s);
     return rc;
@@ -438,9 +639,10 @@ extern "C" int hgx_svd_destroy(hgx_svd *s) {
     hgx_release(l.off);
     hgx_release(l.rows);
   }
-  for (DevBuf *b : {&s->part, &s->gpart, &s->gout, &s->mdev}) hgx_release(*b);
-  if (s->e0) hipEventDestroy(s->e0);
-  if (s->e1) hipEventDestroy(s->e1);
+  for (DevBuf *b : {&s->part, &s->gpart, &s->gout, &s->mdev, &s->cdq, &s->cdviol})
+    hgx_release(*b);
+  for (hipEvent_t e : {s->e0, s->e1, s->c0, s->c1})
+    if (e) hipEventDestroy(e);
   delete s;
   return HGX_OK;
 }
@@ -650,5 +852,95 @@ extern "C" int hgx_svd_last_stats(hgx_svd *s, double *spmm_ms, double *spmm_byte
   if (spmm_calls) *spmm_calls = s->spmm_calls;
   if (spmm_cols) *spmm_cols = s->spmm_cols;
   if (dense_calls) *dense_calls = s->dense_calls;
+  return HGX_OK;
+}
+
+namespace {
+
+// fused: bslot is the other side's panel X and B = A X (A^T X) is formed in
+// the kernel
+int cd_sweep(hgx_svd *s, int pslot, int pcol0, int bslot, int bcol0, int k,
+             const double *Q, double *violation, bool fused) {
+  if (!s) return HGX_EINVAL;
+  hgx_ctx *ctx = s->ctx;
+  Panel *P, *B;
+  HGX_TRY(view(s, pslot, pcol0, k, &P));
+  HGX_TRY(view(s, bslot, bcol0, k, &B));
+  const int32_t *rp = nullptr, *col = nullptr;
+  if (fused) {
+    HGX_CHECK(ctx, P->side != B->side, HGX_EINVAL,
+              "the fused sweep takes the other side's panel as its source");
+    HGX_CHECK(ctx, s->inc_gen == ctx->inc_gen, HGX_ESTATE,
+              "the incidence changed after hgx_svd_create");
+    rp = (P->side ? ctx->rp_n : ctx->rp_e).as<int32_t>();
+    col = (P->side ? ctx->col_n : ctx->col_e).as<int32_t>();
+  } else {
+    HGX_CHECK(ctx, P->side == B->side, HGX_EINVAL, "sweep over panels of two sides");
+    HGX_CHECK(ctx, !overlap(pslot, pcol0, k, bslot, bcol0, k), HGX_EINVAL,
+              "sweep whose factor and product share columns of one panel");
+  }
+  HGX_CHECK(ctx, k <= kCdMaxK, HGX_EUNSUP, "sweep of more than %d columns", kCdMaxK);
+  HGX_CHECK(ctx, Q && violation, HGX_EINVAL, "null matrix or result");
+  for (int64_t i = 0; i < (int64_t)k * k; i++)
+    HGX_CHECK(ctx, std::isfinite(Q[i]), HGX_EVALUE, "the matrix holds a non-finite value");
+  HGX_HIP(ctx, hipSetDevice(ctx->device));
+  const int64_t n = P->rows;
+  std::vector<double> qt((size_t)k * k);
+  for (int t = 0; t < k; t++)
+    for (int r = 0; r < k; r++) qt[(size_t)r * k + t] = Q[(size_t)t * k + r];
+  HGX_TRY(hgx_ensure(ctx, s->cdq, sizeof(double) * qt.size()));
+  HGX_TRY(hgx_ensure(ctx, s->cdviol, sizeof(double) * (size_t)(n + 1)));
+  HGX_HIP(ctx, hipMemcpyAsync(s->cdq.p, qt.data(), sizeof(double) * qt.size(),
+                              hipMemcpyHostToDevice, ctx->stream));
+  int G = 1;
+  while (G < 64 && G < k) G <<= 1;
+  const int R = (k + G - 1) / G;
+  const bool ldsq = sizeof(double) * qt.size() <= kCdLds;
+  float *p = P->buf.as<float>() + pcol0;
+  const float *b = B->buf.as<float>() + bcol0;
+  const int64_t ldp = P->ld, ldb = B->ld;
+  HGX_HIP(ctx, hipEventRecord(s->c0, ctx->stream));
+  if (ldsq) {  // k <= 143: R <= 3
+    if (R == 1) HGX_TRY((launch_cd<1, true>(s, p, ldp, b, ldb, k, n, G, rp, col)));
+    else if (R == 2) HGX_TRY((launch_cd<2, true>(s, p, ldp, b, ldb, k, n, G, rp, col)));
+    else HGX_TRY((launch_cd<3, true>(s, p, ldp, b, ldb, k, n, G, rp, col)));
+  } else {
+    if (R <= 3) HGX_TRY((launch_cd<3, false>(s, p, ldp, b, ldb, k, n, G, rp, col)));
+    else if (R == 4) HGX_TRY((launch_cd<4, false>(s, p, ldp, b, ldb, k, n, G, rp, col)));
+    else if (R <= 6) HGX_TRY((launch_cd<6, false>(s, p, ldp, b, ldb, k, n, G, rp, col)));
+    else HGX_TRY((launch_cd<kCdMaxR, false>(s, p, ldp, b, ldb, k, n, G, rp, col)));
+  }
+  double *sum = s->cdviol.as<double>() + n;
+  hipLaunchKernelGGL(cd_violation, dim3(1), dim3(kCdTB), 0, ctx->stream,
+                     s->cdviol.as<double>(), n, sum);
+  HGX_LAUNCH_CHECK(ctx);
+  HGX_HIP(ctx, hipEventRecord(s->c1, ctx->stream));
+  HGX_HIP(ctx, hipMemcpyAsync(violation, sum, sizeof(double), hipMemcpyDeviceToHost,
+                              ctx->stream));
+  HGX_HIP(ctx, hipStreamSynchronize(ctx->stream));  // qt is read until here
+  float ms = 0;
+  HGX_HIP(ctx, hipEventElapsedTime(&ms, s->c0, s->c1));
+  s->cd_ms += ms;
+  s->cd_sweeps++;
+  return HGX_OK;
+}
+
+}  // namespace
+
+extern "C" int hgx_svd_cd_sweep(hgx_svd *s, int pslot, int pcol0, int bslot, int bcol0,
+                                int k, const double *Q, double *violation) {
+  return cd_sweep(s, pslot, pcol0, bslot, bcol0, k, Q, violation, false);
+}
+
+extern "C" int hgx_svd_cd_sweep_fused(hgx_svd *s, int pslot, int pcol0, int xslot,
+                                      int xcol0, int k, const double *Q,
+                                      double *violation) {
+  return cd_sweep(s, pslot, pcol0, xslot, xcol0, k, Q, violation, true);
+}
+
+extern "C" int hgx_svd_cd_last_stats(hgx_svd *s, double *sweep_ms, int64_t *sweeps) {
+  if (!s) return HGX_EINVAL;
+  if (sweep_ms) *sweep_ms = s->cd_ms;
+  if (sweeps) *sweeps = s->cd_sweeps;
   return HGX_OK;
 }

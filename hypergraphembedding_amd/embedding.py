@@ -11,10 +11,10 @@ Registry and signatures kept for the FOBE/HOBE path: ``Embed(args, hg)``
 incidence upload -> sampler -> records stay in HBM -> tables initialised on
 device -> Keras-semantics fit -> rows idx+1 copied into the proto.
 ``EmbedRandom`` and ``EmbedSvd`` (110-140) live in svd.py; "RANDOM" is
-registered, "SVD" is bound by the integrator. The
-reference's other methods (NMF, node2vec, auto-encoder) are outside this
-hot path: their keys raise like the reference's ``method_not_supported``
-(419-420).
+registered, "SVD" is bound by the integrator, and so
+is "NMF" to ``EmbedNMF`` (143-162, nmf.py). The reference's other methods
+(node2vec, auto-encoder) are outside this hot path: their keys raise like
+the reference's ``method_not_supported`` (419-420).
 """
 
 import logging
@@ -31,6 +31,7 @@ from .hg2v_sample import (_quotas, row_class_quota, sample_fobe, sample_hobe,
 from .hypergraph_util import Incidence
 from .proto import HypergraphEmbedding
 from .runtime import check_rng, get_context, numpy_seed, numpy_state_seed
+from .nmf import EmbedNMF, nmf_incidence
 from .svd import EmbedRandom, EmbedSvd
 
 log = logging.getLogger()
@@ -575,8 +576,9 @@ EMBEDDING_OPTIONS = {
     "HG2V_BOOLEAN_NS": lambda h, d, **kw: EmbedHg2vBoolean(h, d, neg_samples=500,
                                                            **kw),
     # outside the FOBE/HOBE hot path (SURVEY §2 "OUT OF SCOPE"). EmbedSvd
-    # exists (svd.py); a reference-side integrator binds "SVD" to it
-    # (INTEGRATION.md §1), this registry keeps the key unsupported
+    # (svd.py) and EmbedNMF (nmf.py) exist; a reference-side integrator binds
+    # "SVD" and "NMF" to them, this registry keeps both
+    # keys unsupported
     "SVD": method_not_supported,
     "RANDOM": EmbedRandom,
     "NMF": method_not_supported,
@@ -603,4 +605,4 @@ __all__ = ["Embed", "EMBEDDING_OPTIONS", "DEBUG_SUMMARY_OPTIONS",
            "EmbedHg2vAlgDist", "EmbedAlgebraicDistance", "EmbedHg2vAdjJaccard",
            "EmbedHg2vNeighborhoodWeightedJaccard",
            "CombineEmbeddingsViaConcatenation", "method_not_supported",
-           "EmbedSvd", "EmbedRandom"]
+           "EmbedSvd", "EmbedRandom", "EmbedNMF", "nmf_incidence"]

@@ -24,7 +24,8 @@ the smaller side (A^T A when E <= N, otherwise A A^T):
   product. Only that measured figure ends the solve.
 
 The driver talks to a backend with the protocol of ``_hgx.Svd`` (panel, set,
-get, copy, spmm, gram, apply, scale, stats, close and ``rows``);
+get, copy, spmm, gram, apply, scale, stats, close and ``rows``; nmf.py adds
+cd_sweep, cd_sweep_fused and cd_stats);
 ``NumpyBackend`` restates it with numpy / scipy (fp32 panels, float64 sums) so
 that the same driver runs without a GPU in the tests.
 """
@@ -116,6 +117,57 @@ class NumpyBackend:
 
   def stats(self):
     return dict(self._st)
+
+  def cd_sweep(self, pslot, pcol0, bslot, bcol0, Q):
+    """hgx_svd_cd_sweep: one non-negative coordinate-descent sweep of the k
+    columns from pcol0 of pslot (P) against the k columns from bcol0 of bslot
+    (B) and the k x k float64 matrix Q. Every row i on its own, t = 0..k-1 in
+    order, in float64: g = Q[t] . P[i] - B[i][t]; the violation grows by |g|
+    (|min(g, 0)| where P[i][t] == 0); P[i][t] becomes max(P[i][t] - g /
+    Q[t][t], 0) rounded to fp32 (unless Q[t][t] == 0), and the later
+    coordinates see the rounded value. Returns the summed violation."""
+    k = np.shape(Q)[0]
+    assert self.side[pslot] == self.side[bslot]
+    assert pslot != bslot or pcol0 + k <= bcol0 or bcol0 + k <= pcol0
+    return self._sweep(pslot, pcol0, Q,
+                       self.p[bslot][:, bcol0:bcol0 + k].astype(np.float64))
+
+  def cd_sweep_fused(self, pslot, pcol0, xslot, xcol0, Q):
+    """hgx_svd_cd_sweep_fused: cd_sweep with B = A X (factor on the node
+    side) or A^T X formed in float64 from the k columns from xcol0 of xslot,
+    a panel of the other side, and used without rounding it to fp32."""
+    k = np.shape(Q)[0]
+    assert self.side[pslot] != self.side[xslot]
+    m = self.a if self.side[pslot] == NODE else self.at
+    return self._sweep(pslot, pcol0, Q,
+                       m @ self.p[xslot][:, xcol0:xcol0 + k].astype(np.float64))
+
+  def _sweep(self, pslot, pcol0, Q, B):
+    import time
+    t0 = time.perf_counter()
+    Q = np.asarray(Q, np.float64)
+    k = Q.shape[0]
+    assert Q.shape == (k, k)
+    if not np.isfinite(Q).all():
+      raise ValueError("cd_sweep: the matrix holds a non-finite value")
+    P = self.p[pslot][:, pcol0:pcol0 + k]
+    W = P.astype(np.float64)
+    viol = 0.0
+    for t in range(k):
+      g = W @ Q[t] - B[:, t]
+      pt = W[:, t]
+      viol += float(np.abs(np.where(pt == 0.0, np.minimum(g, 0.0), g)).sum())
+      if Q[t, t] != 0.0:
+        W[:, t] = np.maximum(pt - g / Q[t, t], 0.0).astype(np.float32)
+    P[:] = W
+    self._cd_ms = getattr(self, "_cd_ms", 0.0) + (time.perf_counter() - t0) * 1e3
+    self._cd_n = getattr(self, "_cd_n", 0) + 1
+    return viol
+
+  def cd_stats(self):
+    """Host wall time of the sweeps so far (ms) and their count."""
+    return {"sweep_ms": getattr(self, "_cd_ms", 0.0),
+            "sweeps": getattr(self, "_cd_n", 0)}
 
 
 def _inv_factor(C):

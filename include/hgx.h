@@ -548,7 +548,36 @@ int hgx_svc_last_stats(const hgx_svc *s, double *fit_ms, double *decision_ms);
  * hgx_svd_last_stats: device time (ms, HIP events) and algorithmic bytes
  * (4 nnz + 4 b nnz + 4 b rows per product of b columns) summed over the
  * products so far, their count and their total columns, and the count of
- * dense calls (gram, apply, scale). */
+ * dense calls (gram, apply, scale).
+ *
+ * hgx_svd_cd_sweep is the one primitive the NMF baseline adds (EmbedNMF,
+ * reference embedding.py:143-162, sklearn's coordinate-descent solver;
+ * hypergraphembedding_amd/nmf.py drives its fused form with gram): one
+ * non-negative coordinate-descent sweep over every row i of the factor view
+ * P = columns [pcol0, pcol0 + k) of pslot, with B = columns [bcol0, bcol0 +
+ * k) of bslot the matching rows of the sparse product and Q a k x k
+ * row-major float64 host matrix (the other factor's Gram). For t = 0..k-1
+ * in order, in float64:
+ *   g = sum_r Q[t][r] P[i][r] - B[i][t]
+ *   violation += |g|, or |min(g, 0)| where P[i][t] == 0
+ *   if Q[t][t] != 0: P[i][t] <- fp32(max(P[i][t] - g / Q[t][t], 0))
+ * and later coordinates of the row see the rounded value. *violation is the
+ * sum over all rows, one float64 partial per row added in a fixed order (no
+ * atomics). The two views are on the same side, and in one slot only with
+ * disjoint column ranges (HGX_EINVAL); columns outside the factor view are
+ * not touched; a non-finite entry of Q is HGX_EVALUE before any launch.
+ * 1 <= k <= 512 (HGX_EUNSUP above: a lane holds at most 8 coordinates of a
+ * row in registers); Q is staged in LDS up to k = 143 and read through L2
+ * above. The call returns after the sweep has finished.
+ * hgx_svd_cd_sweep_fused is the same sweep with B not read from a panel but
+ * formed inside the kernel: xslot / xcol0 name k columns X of a panel of the
+ * OTHER side (HGX_EINVAL for the same side) and row i of B = A X (factor on
+ * the node side) or A^T X (edge side) is summed in CSR column order in
+ * float64 and used unrounded. This is the form the solver runs: the fp32
+ * rounding of a stored product is its largest error where a badly scaled
+ * component cancels B against the Gram terms.
+ * hgx_svd_cd_last_stats: device time (ms, HIP events) summed over the
+ * sweeps so far, and their count. */
 typedef struct hgx_svd hgx_svd;
 int hgx_svd_create(hgx_ctx *ctx, int long_row, hgx_svd **out);
 int hgx_svd_destroy(hgx_svd *s);
@@ -566,6 +595,12 @@ int hgx_svd_scale(hgx_svd *s, int slot, int col0, int ncols,
 int hgx_svd_last_stats(hgx_svd *s, double *spmm_ms, double *spmm_bytes,
                        int64_t *spmm_calls, int64_t *spmm_cols,
                        int64_t *dense_calls);
+int hgx_svd_cd_sweep(hgx_svd *s, int pslot, int pcol0, int bslot, int bcol0,
+                     int k, const double *Q, double *violation);
+int hgx_svd_cd_sweep_fused(hgx_svd *s, int pslot, int pcol0, int xslot,
+                           int xcol0, int k, const double *Q,
+                           double *violation);
+int hgx_svd_cd_last_stats(hgx_svd *s, double *sweep_ms, int64_t *sweeps);
 
 /* ---- host utilities (bench / test data; not reference entry points) --- *
  * Power-law synthetic incidence of SURVEY.md §8(d) (C4/C5): node degree
