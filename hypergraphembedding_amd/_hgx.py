@@ -107,6 +107,7 @@ SIGNATURES = {
     "hgx_train_last_stats": (_int, [_vp, _pdbl, _pi64, _pi64]),
     "hgx_train_path_stats": (_int, [_vp, _pi64, _pi64]),
     "hgx_train_multi_pending": (_int, [_vp, _pi64]),
+    "hgx_train_step_geometry": (_int, [_vp, _pint, _pint]),
     "hgx_train_last_loss": (_int, [_vp, _pdbl]),
     "hgx_synth_powerlaw": (_int, [_i32, _i32, ctypes.c_double, ctypes.c_double,
                                   _u64, _vp, _vp, _pi64,
@@ -275,9 +276,10 @@ class Context:
   def set_tuning(self, key, value):
     """Pick between exact implementations (hgx_set_tuning): sample_reject_w,
     sample_mode3, sample_mode3_shift, sample_mode3_shift_e, train_fused,
-    train_lanes, train_tb, train_prep_overlap, train_prep_cus, alg_long,
-    alg_ks, alg_push, mlp_fuse_head, mlp_prefetch, mlp_wgrad_split,
-    svc_lds_m, stream_cus."""
+    train_lanes, train_tb, train_wave_pair (1 one record on two waves, 0 off,
+    -1 per geometry), train_prep_overlap, train_prep_cus, alg_long, alg_ks,
+    alg_push, mlp_fuse_head, mlp_prefetch, mlp_wgrad_split, svc_lds_m,
+    stream_cus."""
     self._chk(lib().hgx_set_tuning(self.h, key.encode(), int(value)))
 
   # ---- incidence ----
@@ -678,6 +680,14 @@ class Context:
     v = ctypes.c_int64()
     self._chk(lib().hgx_train_multi_pending(self.h, ctypes.byref(v)))
     return v.value
+
+  def train_step_geometry(self):
+    """(threads, records) per workgroup of the last train()'s deferred-row
+    step, (0, 0) without it; the paired-wave form is (512, 4)."""
+    t, r = ctypes.c_int(), ctypes.c_int()
+    self._chk(lib().hgx_train_step_geometry(self.h, ctypes.byref(t),
+                                            ctypes.byref(r)))
+    return t.value, r.value
 
 
 class Mlp:

@@ -138,6 +138,10 @@ extern "C" int hgx_set_tuning(hgx_ctx *ctx, const char *key, int64_t value) {
     HGX_CHECK(ctx, value == 0 || value == 128 || value == 256 || value == 512, HGX_EINVAL,
               "train_tb must be 0, 128, 256 or 512");
     t.train_tb = (int)value;
+  } else if (k == "train_wave_pair") {
+    HGX_CHECK(ctx, value >= -1 && value <= 1, HGX_EINVAL,
+              "train_wave_pair must be -1, 0 or 1");
+    t.train_wave_pair = (int)value;
   } else if (k == "alg_long") {
     HGX_CHECK(ctx, value == 0 || (value >= 64 && value <= (1 << 20)), HGX_EINVAL,
               "alg_long must be 0 or in [64, 2^20]");

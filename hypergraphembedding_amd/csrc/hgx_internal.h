@@ -56,6 +56,10 @@ struct Tuning {
   // trainer step workgroup size (0 auto; 128 / 256 at 32 lanes, 256 / 512 at
   // 64 lanes x float2; other values fall back to the geometry's default)
   int train_tb = 0;
+  // trainer step at 64 lanes per record: one record on two waves (node half,
+  // edge half), 512 threads = 4 records per workgroup. -1 per geometry, 0 off,
+  // 1 on
+  int train_wave_pair = -1;
   // alg-dist: long-row threshold (0: kLongRow) and coordinate row width
   // (0: round_up(k + 1, 4))
   int alg_long = 0;
@@ -210,6 +214,8 @@ struct hgx_ctx {
   int64_t train_records = 0, train_batches = 0;
   int64_t train_fused = 0, train_split = 0;
   int64_t train_multi = 0;  // step batches in the MULTI pending-slot form
+  // the step's launch geometry of the last hgx_train (0, 0 without the step)
+  int train_step_tb = 0, train_step_rpb = 0;
 
   // ---- scratch ----
   DevBuf s0, s1, s2, s3, s4, s5, s6, s7;
@@ -382,9 +388,14 @@ __device__ __forceinline__ float group_allreduce_sum(float x) {
                " %4, %5\n\t" op " %6, %7"                                  \
                : "+v"(a[i]), "+v"(b[i]), "+v"(a[i + 1]), "+v"(b[i + 1]),      \
                  "+v"(a[i + 2]), "+v"(b[i + 2]), "+v"(a[i + 3]), "+v"(b[i + 3]))
+#define HGX_SWAP2(op)                                                        \
+  asm volatile("s_nop 1\n\t" op " %0, %1\n\t" op " %2, %3"                  \
+               : "+v"(a[i]), "+v"(b[i]), "+v"(a[i + 1]), "+v"(b[i + 1]))
+// N = 4n, or 4n + 2 (the last two values swapped as a pair)
 template <int N>
 __device__ __forceinline__ void wave_allreduce_sum_n(float (&x)[N]) {
-  static_assert(N % 4 == 0, "groups of four");
+  static_assert(N % 2 == 0, "groups of four, then one of two");
+  constexpr int N4 = N / 4 * 4;
 #pragma unroll
   for (int i = 0; i < N; i++) x[i] += dpp_f<0xB1>(x[i]);
 #pragma unroll
@@ -397,15 +408,24 @@ __device__ __forceinline__ void wave_allreduce_sum_n(float (&x)[N]) {
 #pragma unroll
   for (int i = 0; i < N; i++) a[i] = b[i] = x[i];
 #pragma unroll
-  for (int i = 0; i < N; i += 4) HGX_SWAP4("v_permlane16_swap_b32");
+  for (int i = 0; i < N4; i += 4) HGX_SWAP4("v_permlane16_swap_b32");
+  if constexpr (N4 < N) {
+    constexpr int i = N4;
+    HGX_SWAP2("v_permlane16_swap_b32");
+  }
 #pragma unroll
   for (int i = 0; i < N; i++) a[i] = b[i] = a[i] + b[i];
 #pragma unroll
-  for (int i = 0; i < N; i += 4) HGX_SWAP4("v_permlane32_swap_b32");
+  for (int i = 0; i < N4; i += 4) HGX_SWAP4("v_permlane32_swap_b32");
+  if constexpr (N4 < N) {
+    constexpr int i = N4;
+    HGX_SWAP2("v_permlane32_swap_b32");
+  }
 #pragma unroll
   for (int i = 0; i < N; i++) x[i] = a[i] + b[i];
 }
 #undef HGX_SWAP4
+#undef HGX_SWAP2
 
 // Whole-wave min / max without LDS traffic: the four in-row DPP steps, then
 // the four row results by v_readlane (wave-uniform result). ds_bpermute

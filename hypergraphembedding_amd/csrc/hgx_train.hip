@@ -374,6 +374,30 @@ __global__ __launch_bounds__(TB) void train_fwd_bwd(TrainArgs a, int cb) {
   trace_put(bm.y, 0, 6, ts);
 }
 
+// The step's scalar head math, its float2 dot and its Adagrad updates (in the
+// step and in train_flush, which must agree: a streamed run ends every chunk
+// with a flush where a resident run goes on stepping) with every product that
+// feeds a sum, and the sums of products, compiled with contraction off
+// (these operations carry no `contract` flag, so no fma is formed from them;
+// the __f*_rn functions are plain operators and do contract). The compiler pairs up and contracts these
+// few scalar operations differently in every instantiation (y3 - yt3 was an
+// fma at float4 rows and a packed subtraction at float2 rows; the paired-wave
+// form, with half the heads per wave, chose differently again), and the
+// step's forms must agree bit for bit (tests/test_gpu_train_pair.py). The
+// oracle rounds each operation too.
+__device__ __forceinline__ float mul_nc(float x, float y) {
+#pragma clang fp contract(off)
+  return x * y;
+}
+__device__ __forceinline__ float add_nc(float x, float y) {
+#pragma clang fp contract(off)
+  return x + y;
+}
+__device__ __forceinline__ float sub_nc(float x, float y) {
+#pragma clang fp contract(off)
+  return x - y;
+}
+
 // Adagrad on one float4 of a row (Keras 2.x formulas, round-to-nearest ops
 // so the device matches the oracle's rounding)
 __device__ __forceinline__ void adagrad4(float4 &p, float4 &ac, float4 g,
@@ -398,10 +422,10 @@ __device__ __forceinline__ void adagrad4_hw(float4 &p, float4 &ac, float4 g,
   const float *gv = &g.x;
 #pragma unroll
   for (int c = 0; c < 4; c++) {
-    const float na = __fadd_rn(aa[c], __fmul_rn(gv[c], gv[c]));
+    const float na = add_nc(aa[c], mul_nc(gv[c], gv[c]));
     aa[c] = na;
-    const float den = __fadd_rn(__builtin_amdgcn_sqrtf(na), eps);
-    pp[c] = __fsub_rn(pp[c], __fmul_rn(__fmul_rn(lr, gv[c]), __builtin_amdgcn_rcpf(den)));
+    const float den = add_nc(__builtin_amdgcn_sqrtf(na), eps);
+    pp[c] = sub_nc(pp[c], mul_nc(mul_nc(lr, gv[c]), __builtin_amdgcn_rcpf(den)));
   }
 }
 
@@ -580,6 +604,25 @@ __device__ __forceinline__ unsigned long long to_fix(float v) {
 __device__ __forceinline__ float from_fix(long long v) {
   return (float)((double)v * kFixInv);
 }
+// The step's scalar head math (contraction off, see mul_nc)
+__device__ __forceinline__ float act_d_nc(int act, float z, float y) {
+  return act == 0 ? mul_nc(y, sub_nc(1.0f, y)) : (z > 0.f ? 1.f : 0.f);
+}
+__device__ __forceinline__ void head_loss_nc(int loss, float y, float yt,
+                                             float &lv, float &g) {
+  const float eps = 1e-7f;
+  if (loss == 0) {  // KLD with Keras clipping
+    const float ytc = fminf(fmaxf(yt, eps), 1.f);
+    const float ypc = fminf(fmaxf(y, eps), 1.f);
+    lv = mul_nc(ytc, logf(ytc / ypc));
+    g = (y >= eps && y <= 1.f) ? -ytc / ypc : 0.f;
+  } else {  // MSE
+    const float df = sub_nc(y, yt);
+    lv = mul_nc(df, df);
+    g = 2.f * df;
+  }
+}
+
 // The step's per-lane vector: VW floats of a row (float4: dp = 4L, float2:
 // dp = 2L), the fixed-point view of this lane's part of a gacc entry, and the
 // ops on them
@@ -644,16 +687,20 @@ struct SV<2> {
   static __device__ __forceinline__ T fma(float s, T v, T c) {
     return make_float2(fmaf(s, v.x, c.x), fmaf(s, v.y, c.y));
   }
-  static __device__ __forceinline__ float dot(T x, T y) { return x.x * y.x + x.y * y.y; }
+  // (contraction off: two products and their sum, each rounded, in every
+  // form of the step; see mul_nc)
+  static __device__ __forceinline__ float dot(T x, T y) {
+    return add_nc(mul_nc(x.x, y.x), mul_nc(x.y, y.y));
+  }
   static __device__ __forceinline__ void adagrad(T &p, T &ac, T g, float lr, float eps) {
     const float *gv = &g.x;
     float *pp = &p.x, *aa = &ac.x;
 #pragma unroll
     for (int c = 0; c < 2; c++) {
-      const float na = __fadd_rn(aa[c], __fmul_rn(gv[c], gv[c]));
+      const float na = add_nc(aa[c], mul_nc(gv[c], gv[c]));
       aa[c] = na;
-      const float den = __fadd_rn(__builtin_amdgcn_sqrtf(na), eps);
-      pp[c] = __fsub_rn(pp[c], __fmul_rn(__fmul_rn(lr, gv[c]), __builtin_amdgcn_rcpf(den)));
+      const float den = add_nc(__builtin_amdgcn_sqrtf(na), eps);
+      pp[c] = sub_nc(pp[c], mul_nc(mul_nc(lr, gv[c]), __builtin_amdgcn_rcpf(den)));
     }
   }
   static __device__ __forceinline__ void pin(T &v) { asm volatile("" : "+v"(v.x), "+v"(v.y)); }
@@ -832,8 +879,342 @@ __device__ __forceinline__ void row0_finish(const TrainArgs &a, int q,
 #ifndef HGX_TRAIN_R0EARLY
 #define HGX_TRAIN_R0EARLY 1
 #endif
-template <int L, int VW, int KMAX, int MODE, int TB, bool MULTI>
+
+// The paired-wave form of the step (PAIR, 64 lanes per record, 512 threads):
+// one record on two waves of the workgroup, wave 2g the node half of record
+// g and wave 2g + 1 its edge half, still 4 records per workgroup and the same
+// placed buffers. The two halves of a record are the same program on
+// different tables: a hub row H (Nl / Er), the other head row O (Nr / El) and
+// K list rows Tk, with z = H.O, zk = Tk.H, the gradients gH = dz O + sum dk
+// Tk, gO = dz H, gk = dk H, emitted lists first, then H, then O (the
+// unpaired emit order restricted to one table). They meet in three scalars
+// exchanged through LDS across one workgroup barrier: P = mean act(za) from
+// the node wave, Q = mean act(zb) and y2 from the edge wave (y2, not l2: the
+// node wave has the target and forms l2 and l1 + l2 + l3 as the one-wave form
+// does). Repeated rows (s_gl, indexed by the owner's slot number), deferred
+// rows, pending slots and the padding-row sums are all per table, so no other
+// state crosses the pair. Own slots are j = 0 (H), 1 (O), 2 + k (Tk).
+template <int VW, int K, int MODE, bool MULTI>
+__device__ __forceinline__ void train_step_pair(const TrainArgs &a, int cb, int gb, int nb,
+                                                int q) {
+  constexpr int L = 64, RPB = 4, NW = 2 * RPB, TB = NW * L, R = 4 + 2 * K, J = 2 + K;
+  constexpr int NZ = 1 + K;  // head dots of one half
+  using S = SV<VW>;
+  using V = typename S::T;
+  static_assert(R + kWX <= 32, "slot and batch words fit the first 32 lanes");
+  static_assert(NZ % 2 == 0, "the head dots reduce in groups of four, then two");
+  constexpr bool kR0E = HGX_TRAIN_R0EARLY && VW == 2;
+  __shared__ V s_z[2][RPB][L];
+  __shared__ V s_gl[RPB][R][L];  // gradients of local (one-record) rows
+  __shared__ V s_r0[2][L];
+  __shared__ float s_loss[RPB];
+  __shared__ float s_x[RPB][4];  // P, Q, y2 of each record
+  unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (g_trace) ts[0] = __builtin_amdgcn_s_memrealtime();
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / L), lane = threadIdx.x % L;
+  const int grp = wave >> 1, half = wave & 1;  // half 1: the edge wave
+  const bool edge = half;
+  const int NBF = gridDim.x, RW = a.RW;
+  const int par = q % 3, ppar = (q + 2) % 3, zpar = (q + 1) % 3;
+  // round trip 1: as the unpaired form, both waves of a pair loading their
+  // record's words; the padding-row loads by the column owners only (waves
+  // 0 and 1: the node and the edge table's row 0)
+  const size_t gi = ((size_t)cb * NBF + blockIdx.x) * RPB + grp;
+  const int *ri = a.pidx + gi * RW;
+  const unsigned *rc = a.pcode + gi * RW;
+  const float *yt = a.ptgt + gi * 3;
+  const int sl = lane < RW ? lane : 0;
+  const int rv = ri[sl];
+  const int cv = (int)rc[sl];
+  const int tv = __float_as_int(yt[lane < 3 ? lane : 0]);
+  // (no default values, see flush slot 0 below)
+  Row0Loads<L, VW> r0l;
+  if (wave < 2) row0_issue<L, VW>(a, q, r0l);
+  int row[J], frow[kFX];
+  unsigned code[J], fcode[kFX];
+  const int sH = edge ? 3 : 0, sO = edge ? 1 : 2, sT = 4 + half * K;
+  auto slot_of = [&](int j) { return j == 0 ? sH : j == 1 ? sO : sT + j - 2; };
+#pragma unroll
+  for (int j = 0; j < J; j++) {
+    row[j] = __builtin_amdgcn_readlane(rv, slot_of(j));
+    code[j] = (unsigned)__builtin_amdgcn_readlane(cv, slot_of(j));
+  }
+#pragma unroll
+  for (int f = 0; f < kFX; f++) {
+    frow[f] = __builtin_amdgcn_readlane(rv, R + f);
+    fcode[f] = (unsigned)__builtin_amdgcn_readlane(cv, R + f);
+  }
+  const int nfo = __builtin_amdgcn_readlane(rv, R + kFX);
+  const int zc = __builtin_amdgcn_readlane(rv, R + kFX + 1);
+  const float yt0 = __int_as_float(__builtin_amdgcn_readlane(tv, 0));
+  const float yt1 = __int_as_float(__builtin_amdgcn_readlane(tv, 1));
+  const float yt2 = __int_as_float(__builtin_amdgcn_readlane(tv, 2));
+  HGX_STAMP(ts[1]);
+  const int nval = min(max(nb - (int)blockIdx.x + NBF - 1, 0) / NBF, RPB);
+  const bool has = grp < nval;
+  int bad = 0;
+  if (nval > 0) {
+    // round trip 2: this wave's table only
+    // (the table picked once: tab_row's four-way select on a runtime table
+    // bit became a pointer table in scratch)
+    V *Tw = reinterpret_cast<V *>(edge ? a.etab : a.ntab);
+    V *Aw = reinterpret_cast<V *>(edge ? a.eacc : a.nacc);
+    const V *T = Tw, *Ac = Aw;
+    V Pv[J], Av[J];
+    bool lists = false;
+#pragma unroll
+    for (int j = 2; j < J; j++) lists |= row[j] != 0;
+    auto gather = [&](int j) {
+      const int arow = (code[j] & kSOwn) ? row[j] : 0;
+      Pv[j] = T[(size_t)row[j] * L + lane];
+      Av[j] = Ac[(size_t)arow * L + lane];
+    };
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+      if (row[j] == 0) {  // a padding slot: its value comes from s_r0 below
+        Pv[j] = Av[j] = S::zero();
+        continue;
+      }
+      gather(j);
+    }
+    if (lists) {
+#pragma unroll
+      for (int j = 2; j < J; j++) gather(j);
+    }
+    // flush slot 0 rides on the same round trip, on the wave of its table
+    const bool fmine = frow[0] != 0 && (bool)(fcode[0] & kFEdge) == edge;
+    V fp, fa;
+    typename S::Fx fg;
+    if (fmine) {
+      const int mf = (fcode[0] >> kDefBits) & kDefMask;
+      fp = sh_row<L, VW>(a, ppar, mf, 0)[lane];
+      fa = sh_row<L, VW>(a, ppar, mf, 1)[lane];
+      fg = S::ldfix(gacc_row<L, VW>(a, ppar, mf), lane);
+    }
+    if (wave < 2) {
+      V p0 = r0l.rp, a0 = r0l.ra;
+      S::pin(p0);
+      S::pin(a0);
+      row0_finish<L, VW>(a, q, r0l, p0, a0);
+      s_r0[wave][lane] = p0;
+      if (blockIdx.x == 0) {
+        st_row(&sh_row<L, VW>(a, par, wave, 0)[lane], p0);
+        st_row(&sh_row<L, VW>(a, par, wave, 1)[lane], a0);
+      }
+    }
+    __syncthreads();  // s_r0
+    HGX_STAMP(ts[2]);
+    if (has && fmine) {
+      fold<VW>(fp, fa, fg, a.lr, a.eps);
+      st_row(&Tw[(size_t)frow[0] * L + lane], fp);
+      st_row(&Aw[(size_t)frow[0] * L + lane], fa);
+    }
+    // pending slots of this wave's table (entries are rows of one table)
+    unsigned pm = 0;
+#pragma unroll
+    for (int j = 0; j < J; j++)
+      if (code[j] & kSPend) pm |= 1u << j;
+    if (!has) pm = 0;
+    auto fold_pass = [&]() {
+      if (pm == 0) return;
+      const int ps = __builtin_ctz(pm);
+      unsigned cd = 0;
+#pragma unroll
+      for (int j = 0; j < J; j++)
+        if (j == ps) cd = code[j];
+      const unsigned mp = (cd >> kDefBits) & kDefMask;
+      const typename S::Fx gg = S::ldfix(gacc_row<L, VW>(a, ppar, mp), lane);
+      V pp = sh_row<L, VW>(a, ppar, mp, 0)[lane], aa = sh_row<L, VW>(a, ppar, mp, 1)[lane];
+      unsigned wm = 0;
+#pragma unroll
+      for (int j = 0; j < J; j++)
+        if (((code[j] >> kDefBits) & kDefMask) == mp) wm |= 1u << j;
+      wm &= pm;
+      fold<VW>(pp, aa, gg, a.lr, a.eps);
+#pragma unroll
+      for (int j = 0; j < J; j++)
+        if ((wm >> j) & 1u) {
+          Pv[j] = pp;
+          Av[j] = aa;
+        }
+      pm &= ~wm;
+    };
+    fold_pass();
+    if (MULTI) {
+      fold_pass();
+      if (pm != 0) {
+#pragma unroll
+        for (int j = 0; j < J; j++) {
+          if (!((pm >> j) & 1u)) continue;
+          const int mp = (code[j] >> kDefBits) & kDefMask;
+          const typename S::Fx gg = S::ldfix(gacc_row<L, VW>(a, ppar, mp), lane);
+          V pp = sh_row<L, VW>(a, ppar, mp, 0)[lane], aa = sh_row<L, VW>(a, ppar, mp, 1)[lane];
+          fold<VW>(pp, aa, gg, a.lr, a.eps);
+          Pv[j] = pp;
+          Av[j] = aa;
+        }
+      }
+    }
+    // forward, this wave's 1 + K head dots reduced together
+    const int act = MODE == 1 ? 0 : 1;
+    const int lossk = MODE == 1 ? 0 : 1;
+    float zh = 0.f, yh = 0.f, zk[K], sk[K];
+    if (has) {
+#pragma unroll
+      for (int j = 0; j < J; j++)
+        if (row[j] == 0) Pv[j] = s_r0[half][lane];
+      float zz[NZ];
+      zz[0] = S::dot(Pv[0], Pv[1]);
+#pragma unroll
+      for (int k = 0; k < K; k++) zz[1 + k] = S::dot(Pv[2 + k], Pv[0]);
+      hgx::wave_allreduce_sum_n<NZ>(zz);
+      zh = zz[0];
+      yh = act_f(act, zh);
+      float PQ = 0.f;
+#pragma unroll
+      for (int k = 0; k < K; k++) {
+        zk[k] = zz[1 + k];
+        sk[k] = act_f(act, zk[k]);
+        PQ += sk[k];
+      }
+      PQ = PQ / (float)K;
+      if (lane == 0) {
+        s_x[grp][half] = PQ;
+        if (edge) s_x[grp][2] = yh;
+      }
+    }
+    __syncthreads();  // s_x (reached by every wave, with a record or not)
+    V zT = S::zero();  // this table's padding-row gradient sum
+    float lrec = 0.f;
+    if (has) {
+      const float inv_b = 1.0f / (float)nb;
+      const V &H = Pv[0], &O = Pv[1];
+      const float P = s_x[grp][0], Q = s_x[grp][1];
+      const float y3 = mul_nc(P, Q);
+      float lh, l3, gh, g3;
+      head_loss_nc(lossk, yh, edge ? yt1 : yt0, lh, gh);
+      head_loss_nc(lossk, y3, yt2, l3, g3);
+      if (!edge) {
+        const float y1 = yh, y2 = s_x[grp][2];
+        float l1, l2, g1, g2;
+        head_loss_nc(lossk, y1, yt0, l1, g1);
+        head_loss_nc(lossk, y2, yt1, l2, g2);
+        lrec = add_nc(add_nc(l1, l2), l3);
+      }
+      HGX_STAMP(ts[3]);
+      gh *= inv_b;
+      g3 *= inv_b;
+      const float dz = gh * act_d_nc(act, zh, yh);
+      // dP = g3 Q / K on the node wave, dQ = g3 P / K on the edge wave
+      const float dk = g3 * (edge ? P : Q) / (float)K;
+      auto emit = [&](int j, V g) {
+        const unsigned cd = code[j];
+        if (row[j] == 0) {
+          if (!kR0E) zT = S::add(zT, g);
+        } else if (cd & kSLocal) {
+          V *acc = &s_gl[grp][cd & 15u][lane];
+          if (cd & kSOwn) {
+            V pv = Pv[j], av = Av[j];
+            S::adagrad(pv, av, S::add(*acc, g), a.lr, a.eps);
+            st_row(&Tw[(size_t)row[j] * L + lane], pv);
+            st_row(&Aw[(size_t)row[j] * L + lane], av);
+          } else {
+            *acc = (cd & kSFirst) ? g : S::add(*acc, g);
+          }
+        } else if (cd & kSShared) {
+          const int m = cd & kDefMask;
+          S::addfix(gacc_row<L, VW>(a, par, m), lane, g, bad);
+          if (cd & kSOwn) {
+            st_row(&sh_row<L, VW>(a, par, m, 0)[lane], Pv[j]);
+            st_row(&sh_row<L, VW>(a, par, m, 1)[lane], Av[j]);
+          }
+        } else {
+          V pv = Pv[j], av = Av[j];
+          S::adagrad(pv, av, g, a.lr, a.eps);
+          st_row(&Tw[(size_t)row[j] * L + lane], pv);
+          st_row(&Aw[(size_t)row[j] * L + lane], av);
+        }
+      };
+      V gH = S::fma(dz, O, S::zero());
+      if (kR0E) {
+        float d[K];
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+          d[k] = dk * act_d_nc(act, zk[k], sk[k]);
+          gH = S::fma(d[k], Pv[2 + k], gH);
+          if (row[2 + k] == 0) zT = S::add(zT, S::fma(d[k], H, S::zero()));
+        }
+        if (row[0] == 0) zT = S::add(zT, gH);
+        if (row[1] == 0) zT = S::add(zT, S::fma(dz, H, S::zero()));
+        const int slot = (blockIdx.x * RPB + grp) % R0S<VW * L>::n;
+        S::addfix(r0_row<L, VW>(a, par, slot, half), lane, zT, bad);
+        if (!edge && lane == 0)
+          a.lossbuf[(size_t)gb * a.lstride + blockIdx.x * RPB + grp] = lrec;
+#pragma unroll
+        for (int k = 0; k < K; k++) emit(2 + k, S::fma(d[k], H, S::zero()));
+      } else {
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+          const float d = dk * act_d_nc(act, zk[k], sk[k]);
+          gH = S::fma(d, Pv[2 + k], gH);
+          emit(2 + k, S::fma(d, H, S::zero()));
+        }
+      }
+      emit(0, gH);
+      emit(1, S::fma(dz, H, S::zero()));
+      HGX_STAMP(ts[4]);
+    }
+    if (!kR0E) {
+      s_z[half][grp][lane] = zT;
+      if (!edge && lane == 0) s_loss[grp] = lrec;
+      __syncthreads();
+      // the workgroup's fixed-order sum over its records, as the unpaired form
+      if (wave < 2) {
+        V sz = S::zero();
+        for (int g = 0; g < RPB; g++) sz = S::add(sz, s_z[wave][g][lane]);
+        S::addfix(r0_row<L, VW>(a, par, blockIdx.x % R0S<VW * L>::n, wave), lane, sz, bad);
+      }
+      if (threadIdx.x == 0) {
+        float sl = 0.f;
+        for (int g = 0; g < RPB; g++) sl += s_loss[g];
+        a.lossbuf[(size_t)gb * a.lstride + blockIdx.x] = sl;
+      }
+    }
+    // flush slots 1.., dealt over the two waves of the record
+#pragma unroll
+    for (int f = 1; f < kFX; f++)
+      if (frow[f] != 0 && (f & 1) == half)
+        flush_row<L, VW>(a, ppar, (fcode[f] & kFEdge ? 1 << 30 : 0) | frow[f],
+                         (fcode[f] >> kDefBits) & kDefMask, lane);
+  }
+  HGX_STAMP(ts[5]);
+  // flush overflow list and the zeroing loops, over all waves
+  for (int e = blockIdx.x * NW + wave; e < nfo; e += NBF * NW) {
+    const int2 en = a.pfo[(size_t)cb * a.Mmax + e];
+    flush_row<L, VW>(a, ppar, en.x, en.y, lane);
+  }
+  {
+    longlong2 *z = reinterpret_cast<longlong2 *>(gacc_row<L, VW>(a, zpar, 2));
+    const int tot = zc * (VW / 2) * L;
+    for (int i = blockIdx.x * TB + threadIdx.x; i < tot; i += NBF * TB)
+      z[i] = make_longlong2(0, 0);
+    longlong2 *zr = reinterpret_cast<longlong2 *>(r0_row<L, VW>(a, zpar, 0, 0));
+    for (int i = blockIdx.x * TB + threadIdx.x; i < R0S<VW * L>::n * VW * L; i += NBF * TB)
+      zr[i] = make_longlong2(0, 0);
+  }
+  if (__any(bad) && !g_tab && lane == 0) atomicOr(a.ovf, 1);
+  HGX_STAMP(ts[6]);
+  trace_put(gb, 0, 7, ts);
+}
+
+// PAIR: the paired-wave form above (L = 64, TB = 512, 4 records per workgroup)
+template <int L, int VW, int KMAX, int MODE, int TB, bool MULTI, bool PAIR = false>
 __global__ __launch_bounds__(TB) void train_step(TrainArgs a, int cb, int gb, int nb, int q) {
+  if constexpr (PAIR) {
+    static_assert(!PAIR || (L == 64 && TB == 512), "paired geometry");
+    train_step_pair<VW, KMAX, MODE, MULTI>(a, cb, gb, nb, q);
+    return;
+  }
   constexpr int RPB = TB / L, R = 4 + 2 * KMAX, K = KMAX, NC = 2 * L;
   using S = SV<VW>;
   using V = typename S::T;
@@ -1101,18 +1482,18 @@ __global__ __launch_bounds__(TB) void train_step(TrainArgs a, int cb, int gb, in
       }
       P = P / (float)K;
       Q = Q / (float)K;
-      const float y3 = P * Q;
+      const float y3 = mul_nc(P, Q);
       float l1, l2, l3, g1, g2, g3;
-      head_loss(lossk, y1, yt0, l1, g1);
-      head_loss(lossk, y2, yt1, l2, g2);
-      head_loss(lossk, y3, yt2, l3, g3);
-      lrec = l1 + l2 + l3;
+      head_loss_nc(lossk, y1, yt0, l1, g1);
+      head_loss_nc(lossk, y2, yt1, l2, g2);
+      head_loss_nc(lossk, y3, yt2, l3, g3);
+      lrec = add_nc(add_nc(l1, l2), l3);
       HGX_STAMP(ts[3]);
       g1 *= inv_b;
       g2 *= inv_b;
       g3 *= inv_b;
-      const float dz1 = g1 * act_d(act, z1, y1);
-      const float dz2 = g2 * act_d(act, z2, y2);
+      const float dz1 = g1 * act_d_nc(act, z1, y1);
+      const float dz2 = g2 * act_d_nc(act, z2, y2);
       const float dP = g3 * Q / (float)K, dQ = g3 * P / (float)K;
       auto emit = [&](int s, V g) {
         const unsigned cd = code[s];
@@ -1163,8 +1544,8 @@ __global__ __launch_bounds__(TB) void train_step(TrainArgs a, int cb, int gb, in
         float da[K], db[K];
 #pragma unroll
         for (int k = 0; k < K; k++) {
-          da[k] = dP * act_d(act, za[k], sa[k]);
-          db[k] = dQ * act_d(act, zb[k], sb[k]);
+          da[k] = dP * act_d_nc(act, za[k], sa[k]);
+          db[k] = dQ * act_d_nc(act, zb[k], sb[k]);
           gln = S::fma(da[k], Pv[4 + k], gln);
           gre = S::fma(db[k], Pv[4 + K + k], gre);
           if (row[4 + k] == 0) zN = S::add(zN, S::fma(da[k], Nl, S::zero()));
@@ -1186,8 +1567,8 @@ __global__ __launch_bounds__(TB) void train_step(TrainArgs a, int cb, int gb, in
       } else {
 #pragma unroll
         for (int k = 0; k < K; k++) {
-          const float da = dP * act_d(act, za[k], sa[k]);
-          const float db = dQ * act_d(act, zb[k], sb[k]);
+          const float da = dP * act_d_nc(act, za[k], sa[k]);
+          const float db = dQ * act_d_nc(act, zb[k], sb[k]);
           gln = S::fma(da, Pv[4 + k], gln);
           gre = S::fma(db, Pv[4 + K + k], gre);
           emit(4 + k, S::fma(da, Nl, S::zero()));
@@ -1963,10 +2344,22 @@ void step_fns(int loss, KStepFn *kf, KFlushFn &kfl) {
                     : train_step<SL, VW, 5, 2, TB, true>;
   kfl = train_flush<SL * VW / 4>;
 }
+template <int VW>
+void step_fns_pair(int loss, KStepFn *kf, KFlushFn &kfl) {
+  kf[0] = loss == 0 ? train_step<64, VW, 5, 1, 512, false, true>
+                    : train_step<64, VW, 5, 2, 512, false, true>;
+  kf[1] = loss == 0 ? train_step<64, VW, 5, 1, 512, true, true>
+                    : train_step<64, VW, 5, 2, 512, true, true>;
+  kfl = train_flush<64 * VW / 4>;
+}
+// the paired-wave form's default per row width (interleaved A/B)
+constexpr int kPairDefault128 = 1, kPairDefault256 = 1;
 // lanes = the tuning (0 auto, 32 or 64 lanes per record where dp = 128);
-// sets sl (the step's lanes per record), tb and the kernels
-bool pick_step(int L, int VPL, int K, int loss, int act, int lanes, int &sl,
-               int &tb, KStepFn *kf, KFlushFn &kfl) {
+// sets sl (the step's lanes per record), tb, rpb (records per workgroup) and
+// the kernels. pair = the tuning (-1 per geometry): at 64 lanes per record the
+// paired-wave form, 512 threads for 4 records.
+bool pick_step(int L, int VPL, int K, int loss, int act, int lanes, int pair, int &sl,
+               int &tb, int &rpb, KStepFn *kf, KFlushFn &kfl) {
   if (VPL != 1 || K != 5 || loss != act) return false;
   if (L != 32 && L != 64) return false;
   // dp = 128, measured r02 (tools/ab_train.py, interleaved, us per batch on
@@ -1974,6 +2367,15 @@ bool pick_step(int L, int VPL, int K, int loss, int act, int lanes, int &sl,
   // float4 x 32 lanes at 128 threads 8.07 / 8.42 (8.33 / 8.75 at 256)
   const int vw = L == 32 && lanes != 32 ? 2 : 4;
   sl = L * 4 / vw;
+  // (an explicit train_tb keeps the one-wave form it names)
+  const int pair_auto = tb != 0 ? 0 : vw == 2 ? kPairDefault128 : kPairDefault256;
+  if (sl == 64 && (pair < 0 ? pair_auto : pair)) {
+    tb = 512;
+    rpb = 4;
+    if (vw == 2) step_fns_pair<2>(loss, kf, kfl);
+    else step_fns_pair<4>(loss, kf, kfl);
+    return true;
+  }
   if (sl == 32) {
     tb = tb == 256 ? 256 : 128;
     if (tb == 128) step_fns<32, 4, 128>(loss, kf, kfl);
@@ -1987,6 +2389,7 @@ bool pick_step(int L, int VPL, int K, int loss, int act, int lanes, int &sl,
     tb = 256;
     step_fns<64, 4, 256>(loss, kf, kfl);
   }
+  rpb = tb / sl;
   return true;
 }
 
@@ -2434,12 +2837,12 @@ extern "C" int hgx_train(hgx_ctx *ctx, int batch, int max_epochs, float lr,
   KStepFn kf[2] = {nullptr, nullptr};  // light / MULTI pending-slot forms
   KFlushFn kfl = nullptr;
   int tbf = ctx->tune.train_tb;  // workgroup size (0: per geometry)
-  int SL = 0;
+  int SL = 0, rpbf = 0;  // lanes per record, records per workgroup
   const bool fused = ctx->tune.train_fused && env_int("HGX_TRAIN_GENERIC", 0) != 1 &&
                      batch <= kPackB &&
-                     pick_step(L, VPL, K, loss, act, ctx->tune.train_lanes, SL, tbf,
-                               kf, kfl);
-  const int prpb = fused ? tbf / SL : 0;
+                     pick_step(L, VPL, K, loss, act, ctx->tune.train_lanes,
+                               ctx->tune.train_wave_pair, SL, tbf, rpbf, kf, kfl);
+  const int prpb = fused ? rpbf : 0;
   const int NBF = fused ? (batch + prpb - 1) / prpb : 0;
   const int RW = R + kWX;
   const int Mmax = SB / 2 + 1;        // deferred rows per batch: <= SB / 2
@@ -2919,6 +3322,8 @@ extern "C" int hgx_train(hgx_ctx *ctx, int batch, int max_epochs, float lr,
   ctx->train_fused = nfused;
   ctx->train_split = nsplit;
   ctx->train_multi = nmulti;
+  ctx->train_step_tb = fused ? tbf : 0;
+  ctx->train_step_rpb = prpb;
   if (epochs_run) *epochs_run = ep;
   return HGX_OK;
 }
@@ -2941,6 +3346,13 @@ extern "C" int hgx_train_last_loss(hgx_ctx *ctx, double *loss_sum) {
 extern "C" int hgx_train_multi_pending(hgx_ctx *ctx, int64_t *batches) {
   if (!ctx) return HGX_EINVAL;
   if (batches) *batches = ctx->train_multi;
+  return HGX_OK;
+}
+
+extern "C" int hgx_train_step_geometry(hgx_ctx *ctx, int *threads, int *records) {
+  if (!ctx) return HGX_EINVAL;
+  if (threads) *threads = ctx->train_step_tb;
+  if (records) *records = ctx->train_step_rpb;
   return HGX_OK;
 }
 

@@ -77,6 +77,13 @@ int hgx_mem_info(hgx_ctx *ctx, int64_t *free_bytes, int64_t *total_bytes);
  *                      (0 auto = 64, 32 = float4 per lane, 64 = float2)
  *   "train_tb"         fused step workgroup size (0 auto, 128, 256, 512;
  *                      a size the geometry has no form for -> its default)
+ *   "train_wave_pair"  fused step at 64 lanes per record (padded d = 128 or
+ *                      256): 1 one record on two waves of a 512-thread
+ *                      workgroup (the node wave owns the node-table slots,
+ *                      the edge wave the edge-table slots; still 4 records
+ *                      per workgroup; overrides train_tb), 0 one wave per
+ *                      record, -1 per geometry where train_tb is 0 (default);
+ *                      bit-identical
  *   "alg_long"         alg-dist long-row threshold (0 = 512, else >= 64)
  *   "alg_ks"           alg-dist coordinate row width in floats (0 = auto:
  *                      round_up(k + 1, 4), widened from 12 to 16 floats
@@ -421,6 +428,11 @@ int hgx_train_path_stats(hgx_ctx *ctx, int64_t *fused_batches,
 /* Of the last hgx_train: step batches launched in the MULTI pending-slot form
  * (a record of theirs names two rows deferred by the previous batch). */
 int hgx_train_multi_pending(hgx_ctx *ctx, int64_t *batches);
+/* Of the last hgx_train: the deferred-row step's workgroup size and records
+ * per workgroup (0, 0 if it was not eligible). The paired-wave form is 512
+ * threads for 4 records; the one-wave forms have threads / records = the
+ * lanes per record. */
+int hgx_train_step_geometry(hgx_ctx *ctx, int *threads, int *records);
 /* Sum of the per-record losses (all three heads) of the last epoch of the
  * last hgx_train, in double: epoch loss = sum / records. Consecutive
  * hgx_train calls continue the same model state (tables and Adagrad
