@@ -354,6 +354,42 @@ def test_overlapped_preparation_bitwise_equal(ctx, mode, cus):
   assert np.array_equal(out[0][1], out[1][1])
 
 
+def test_two_kernel_step_across_a_chunk_boundary_bitwise(ctx):
+  """The two-kernel step (d = 8: no deferred-row step) over two prepared
+  chunks: 1,030 batches of 4 with a ragged last one, ids from ~50 rows per
+  table so rows repeat inside a batch. One call equals two consecutive calls
+  split at the chunk boundary (1,024 batches, then the rest) bit for bit:
+  consecutive hgx_train calls continue a model, so the second chunk of the
+  single call must see exactly what a fresh call's first chunk sees."""
+  rs = np.random.RandomState(17)
+  K, B, d, nb = 2, 4, 8, 1030
+  n = nb * B - 3
+  idx = rs.randint(0, 51, (n, 4 + 2 * K)).astype(np.int32)
+  tgt = rs.uniform(0, 1, (n, 3)).astype(np.float32)
+  nt = rs.uniform(-0.05, 0.05, (51, d)).astype(np.float32)
+  et = rs.uniform(-0.05, 0.05, (51, d)).astype(np.float32)
+
+  def run(parts):
+    ctx.model_init(d, 51, 51, node_tab=nt, edge_tab=et)
+    lsum, stats = 0.0, None
+    for lo, hi in parts:
+      ctx.records_set(idx[lo:hi], tgt[lo:hi])
+      ctx.train(batch=B, max_epochs=1, loss=O.LOSS_KLD, act=O.ACT_SIGMOID,
+                perms=np.arange(hi - lo)[None, :], min_delta=-1.0)
+      lsum += ctx.train_loss_sum()
+      stats = ctx.train_path_stats()
+    return ctx.model_get() + (lsum, stats)
+
+  one = run([(0, n)])
+  two = run([(0, 1024 * B), (1024 * B, n)])
+  assert one[3] == (0, nb), one[3]
+  assert two[3] == (0, nb - 1024), two[3]
+  assert np.array_equal(one[0], two[0])
+  assert np.array_equal(one[1], two[1])
+  assert not np.array_equal(one[0], nt) and not np.array_equal(one[1], et)
+  assert np.isclose(one[2], two[2], rtol=1e-6), (one[2], two[2])
+
+
 @pytest.mark.parametrize("d", [128, 256])
 def test_padding_row_fixed_point_vs_split_step_and_oracle(ctx, d):
   """The padding row (row 0 of both tables) collects the gradients of every

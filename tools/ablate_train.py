@@ -1,5 +1,5 @@
 """Ablation timing of the batch step (diagnostic build tools/_ab/dbg.so,
-HGX_TRAIN_ABLATE bits, see hgx_train.hip): per-batch device time with one
+HGX_TRAIN_ABLATE bits, see csrc/hgx_train_common.h): per-batch device time with one
 part of the step removed at a time, interleaved over rounds in one process.
 Results are wrong by construction; only the time is read.
   HGX_LIB_PATH=tools/_ab/dbg.so python tools/ablate_train.py [d] [hobe|rand]"""
