@@ -44,6 +44,7 @@ from .embedding import (COMBINATION_OPTIONS, DEBUG_SUMMARY_OPTIONS,
                         EmbedHg2vNeighborhoodWeightedJaccard)
 from .svd import EmbedRandom, EmbedSvd, svd_incidence
 from .nmf import EmbedNMF, nmf_incidence
+from .auto_encoder import EmbedAutoEncoder, auto_encoder_incidence
 
 __all__ = [
     # proto
@@ -56,6 +57,7 @@ __all__ = [
     "EmbedHg2vNeighborhoodWeightedJaccard", "WeightedJaccardSamples",
     # comparison baselines (reference embedding.py:110-162)
     "EmbedSvd", "EmbedRandom", "svd_incidence", "EmbedNMF", "nmf_incidence",
+    "EmbedAutoEncoder", "auto_encoder_incidence",
     # hot-path pieces
     "BooleanSamples", "AlgebraicDistanceSamples", "SamplesToModelInput",
     "SimilarityRecord", "UniformWeight", "WeightByNeighborhood",

@@ -165,6 +165,17 @@ SIGNATURES = {
     "hgx_svd_cd_sweep_fused": (_int, [_vp, _int, _int, _int, _int, _int, _vp,
                                       _pdbl]),
     "hgx_svd_cd_last_stats": (_int, [_vp, _pdbl, _pi64]),
+    "hgx_ae_create": (_int, [_vp, _int, _int, ctypes.POINTER(_vp)]),
+    "hgx_ae_destroy": (_int, [_vp]),
+    "hgx_ae_set_weights": (_int, [_vp, _vp]),
+    "hgx_ae_get_weights": (_int, [_vp, _vp]),
+    "hgx_ae_draw": (_int, [_vp, _i64, _vp, _int, _u64, _int, _pi64, _vp, _vp]),
+    "hgx_ae_step": (_int, [_vp, _i64, _vp, _vp, _f32, _f32,
+                           ctypes.POINTER(_f32)]),
+    "hgx_ae_fit": (_int, [_vp, _int, _int, _int, _f32, _f32, _u64, _vp, _vp,
+                          _pint]),
+    "hgx_ae_encode": (_int, [_vp, _i64, _vp, _vp]),
+    "hgx_ae_last_stats": (_int, [_vp, _pdbl, _pi64, _pi64, _pdbl]),
     "hgx_pyrandom_sample_missing": (_int, [_vp, _i32, _i32, _vp, _vp, _i64,
                                            _vp, _vp, _pi64]),
     "hgx_pyrandom_remove_connections": (_int, [_vp, _i64, _vp, _vp, _vp, _vp,
@@ -279,7 +290,7 @@ class Context:
     train_lanes, train_tb, train_wave_pair (1 one record on two waves, 0 off,
     -1 per geometry), train_prep_overlap, train_prep_cus, alg_long, alg_ks,
     alg_push, mlp_fuse_head, mlp_prefetch, mlp_wgrad_split, svc_lds_m,
-    stream_cus."""
+    ae_chunk_rows, stream_cus."""
     self._chk(lib().hgx_set_tuning(self.h, key.encode(), int(value)))
 
   # ---- incidence ----
@@ -954,6 +965,113 @@ class Svd:
     self.ctx._chk(lib().hgx_svd_cd_last_stats(self.h, ctypes.byref(ms),
                                               ctypes.byref(n)))
     return {"sweep_ms": ms.value, "sweeps": n.value}
+
+
+class Ae:
+  """One hgx_ae engine (include/hgx.h, auto-encoder baseline) on a Context
+  whose incidence is uploaded: the model of one side (0: a row per node, 1: a
+  row per edge) with its Adagrad state on the device. This is the device
+  backend of auto_encoder.auto_encoder_incidence."""
+
+  NODE, EDGE = 0, 1
+
+  def __init__(self, ctx, side, dim):
+    self.ctx, self.side, self.dim = ctx, int(side), int(dim)
+    h = _vp()
+    ctx._chk(lib().hgx_ae_create(ctx.h, self.side, self.dim, ctypes.byref(h)))
+    self.h = h
+    self.R, self.C = ((ctx.inc.E, ctx.inc.N) if self.side
+                      else (ctx.inc.N, ctx.inc.E))
+    ctx._engines.add(self)
+
+  def close(self):
+    if getattr(self, "h", None):
+      lib().hgx_ae_destroy(self.h)
+      self.h = None
+
+  def __del__(self):
+    try:
+      self.close()
+    except Exception:
+      pass
+
+  def __enter__(self):
+    return self
+
+  def __exit__(self, *exc):
+    self.close()
+
+  def num_weights(self):
+    return 2 * self.C * self.dim + self.dim + self.C
+
+  def set_weights(self, W1, b1, W2, b2):
+    flat = np.concatenate([
+        _c(W1, np.float32).reshape(self.C * self.dim),
+        _c(b1, np.float32).reshape(self.dim),
+        _c(W2, np.float32).reshape(self.dim * self.C),
+        _c(b2, np.float32).reshape(self.C)])
+    self.ctx._chk(lib().hgx_ae_set_weights(self.h, _ptr(flat)))
+
+  def get_weights(self):
+    flat = np.empty(self.num_weights(), np.float32)
+    self.ctx._chk(lib().hgx_ae_get_weights(self.h, _ptr(flat)))
+    C, d = self.C, self.dim
+    o = np.cumsum([0, C * d, d, d * C, C])
+    return (flat[o[0]:o[1]].reshape(C, d).copy(), flat[o[1]:o[2]].copy(),
+            flat[o[2]:o[3]].reshape(d, C).copy(), flat[o[3]:o[4]].copy())
+
+  def draw(self, rows, samples_per_idx, seed, epoch):
+    """(row, drop) int32 lists of the listed rows' samples (hgx_ae_draw)."""
+    rows = _c(rows, np.int32).ravel()
+    n = ctypes.c_int64()
+    args = (self.h, rows.size, _ptr(rows), int(samples_per_idx),
+            int(seed) & (2**64 - 1), int(epoch), ctypes.byref(n))
+    self.ctx._chk(lib().hgx_ae_draw(*args, None, None))
+    row = np.empty(n.value, np.int32)
+    drop = np.empty(n.value, np.int32)
+    if n.value:
+      self.ctx._chk(lib().hgx_ae_draw(*args, _ptr(row), _ptr(drop)))
+    return row, drop
+
+  def step(self, row, drop, lr=0.01, eps=1e-7):
+    """One train_on_batch on the explicit sample list; returns the loss."""
+    row, drop = _c(row, np.int32).ravel(), _c(drop, np.int32).ravel()
+    assert row.size == drop.size
+    loss = _f32()
+    self.ctx._chk(lib().hgx_ae_step(self.h, row.size, _ptr(row), _ptr(drop), lr,
+                                    eps, ctypes.byref(loss)))
+    return loss.value
+
+  def fit(self, epochs=5, idx_per_batch=200, samples_per_idx=100, lr=0.01,
+          eps=1e-7, seed=0, perms=None):
+    """hgx_ae_fit; returns the per-batch losses, epochs x sections."""
+    pp = None
+    if perms is not None:
+      pp = _c(perms, np.int64)
+      assert pp.shape == (epochs, self.R)
+    s = max(1, self.R // int(idx_per_batch))
+    losses = np.zeros(max(epochs * s, 1), np.float32)
+    nb = ctypes.c_int()
+    self.ctx._chk(lib().hgx_ae_fit(self.h, int(epochs), int(idx_per_batch),
+                                   int(samples_per_idx), lr, eps,
+                                   int(seed) & (2**64 - 1), _ptr(pp),
+                                   _ptr(losses), ctypes.byref(nb)))
+    return losses[:nb.value].reshape(epochs, s).copy()
+
+  def encode(self, rows):
+    rows = _c(rows, np.int32).ravel()
+    out = np.empty((rows.size, self.dim), np.float32)
+    self.ctx._chk(lib().hgx_ae_encode(self.h, rows.size, _ptr(rows), _ptr(out)))
+    return out
+
+  def stats(self):
+    ms, fl = ctypes.c_double(), ctypes.c_double()
+    sm, bt = ctypes.c_int64(), ctypes.c_int64()
+    self.ctx._chk(lib().hgx_ae_last_stats(self.h, ctypes.byref(ms),
+                                          ctypes.byref(sm), ctypes.byref(bt),
+                                          ctypes.byref(fl)))
+    return {"ms": ms.value, "samples": sm.value, "batches": bt.value,
+            "flops": fl.value}
 
 
 # ---- host utilities (no context, no device) --------------------------------

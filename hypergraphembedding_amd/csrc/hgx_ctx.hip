@@ -162,6 +162,10 @@ extern "C" int hgx_set_tuning(hgx_ctx *ctx, const char *key, int64_t value) {
     HGX_CHECK(ctx, value == 64 || value == 128 || value == 192, HGX_EINVAL,
               "svc_lds_m must be 64, 128 or 192");
     t.svc_lds_m = (int)value;
+  } else if (k == "ae_chunk_rows") {
+    HGX_CHECK(ctx, value >= 0 && value <= (1 << 16), HGX_EINVAL,
+              "ae_chunk_rows must be in [0, 65536]");
+    t.ae_chunk_rows = (int)value;
   } else if (k == "train_prep_overlap") {
     HGX_CHECK(ctx, value >= 0 && value <= 2, HGX_EINVAL, "train_prep_overlap must be 0, 1 or 2");
     t.train_prep_overlap = (int)value;

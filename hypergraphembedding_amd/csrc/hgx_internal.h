@@ -95,6 +95,9 @@ struct Tuning {
   // there); larger problems recompute two kernel columns per iteration.
   // The columns are bitwise the same either way.
   int svc_lds_m = 128;
+  // auto-encoder: rows of one chunk of a batch's logit block (rounded up to
+  // a multiple of 32; 0: sized from the free device memory)
+  int ae_chunk_rows = 0;
 };
 
 struct hgx_ctx {

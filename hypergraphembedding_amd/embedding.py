@@ -12,9 +12,10 @@ incidence upload -> sampler -> records stay in HBM -> tables initialised on
 device -> Keras-semantics fit -> rows idx+1 copied into the proto.
 ``EmbedRandom`` and ``EmbedSvd`` (110-140) live in svd.py; "RANDOM" is
 registered, "SVD" is bound by the integrator, and so
-is "NMF" to ``EmbedNMF`` (143-162, nmf.py). The reference's other methods
-(node2vec, auto-encoder) are outside this hot path: their keys raise like
-the reference's ``method_not_supported`` (419-420).
+is "NMF" to ``EmbedNMF`` (143-162, nmf.py) and "AUTO_ENCODER" to
+``EmbedAutoEncoder`` (auto_encoder.py). The reference's node2vec methods are
+outside this package: their keys raise like the reference's
+``method_not_supported`` (419-420).
 """
 
 import logging
@@ -31,6 +32,7 @@ from .hg2v_sample import (_quotas, row_class_quota, sample_fobe, sample_hobe,
 from .hypergraph_util import Incidence
 from .proto import HypergraphEmbedding
 from .runtime import check_rng, get_context, numpy_seed, numpy_state_seed
+from .auto_encoder import EmbedAutoEncoder, auto_encoder_incidence
 from .nmf import EmbedNMF, nmf_incidence
 from .svd import EmbedRandom, EmbedSvd
 
@@ -576,9 +578,10 @@ EMBEDDING_OPTIONS = {
     "HG2V_BOOLEAN_NS": lambda h, d, **kw: EmbedHg2vBoolean(h, d, neg_samples=500,
                                                            **kw),
     # outside the FOBE/HOBE hot path (SURVEY §2 "OUT OF SCOPE"). EmbedSvd
-    # (svd.py) and EmbedNMF (nmf.py) exist; a reference-side integrator binds
-    # "SVD" and "NMF" to them, this registry keeps both
-    # keys unsupported
+    # (svd.py), EmbedNMF (nmf.py) and EmbedAutoEncoder (auto_encoder.py)
+    # exist; a reference-side integrator binds "SVD", "NMF" and
+    # "AUTO_ENCODER" to them, this registry keeps the
+    # three keys unsupported
     "SVD": method_not_supported,
     "RANDOM": EmbedRandom,
     "NMF": method_not_supported,
@@ -605,4 +608,5 @@ __all__ = ["Embed", "EMBEDDING_OPTIONS", "DEBUG_SUMMARY_OPTIONS",
            "EmbedHg2vAlgDist", "EmbedAlgebraicDistance", "EmbedHg2vAdjJaccard",
            "EmbedHg2vNeighborhoodWeightedJaccard",
            "CombineEmbeddingsViaConcatenation", "method_not_supported",
-           "EmbedSvd", "EmbedRandom", "EmbedNMF", "nmf_incidence"]
+           "EmbedSvd", "EmbedRandom", "EmbedNMF", "nmf_incidence",
+           "EmbedAutoEncoder", "auto_encoder_incidence"]

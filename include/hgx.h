@@ -114,6 +114,9 @@ int hgx_mem_info(hgx_ctx *ctx, int64_t *free_bytes, int64_t *total_bytes);
  *                      batches, bit for bit
  *   "train_prep_cus"   with train_prep_overlap: CUs reserved for the
  *                      preparation stream by disjoint CU masks (0 = no masks)
+ *   "ae_chunk_rows"    auto-encoder: rows of one chunk of a batch's logit
+ *                      block, rounded up to a multiple of 32 (0 = sized from
+ *                      the free device memory, default; at most 65536)
  * Unknown keys and out-of-range values -> HGX_EINVAL. */
 int hgx_set_tuning(hgx_ctx *ctx, const char *key, int64_t value);
 
@@ -613,6 +616,70 @@ int hgx_svd_cd_sweep_fused(hgx_svd *s, int pslot, int pcol0, int xslot,
                            int xcol0, int k, const double *Q,
                            double *violation);
 int hgx_svd_cd_last_stats(hgx_svd *s, double *sweep_ms, int64_t *sweeps);
+
+/* ---- auto-encoder baseline ------------------------------------------------ *
+ * The device half of EmbedAutoEncoder (reference auto_encoder.py:20-115):
+ * one Keras model per side of the incidence uploaded before hgx_ae_create
+ * (HGX_ESTATE without one, or after it was replaced),
+ *   x (C) -> Dense(dim, relu) [W1 C x dim, b1] -> Dense(C, softmax)
+ *   [W2 dim x C, b2], loss kullback_leibler_divergence (both arguments
+ *   clipped to [1e-7, 1], batch mean), optimizer Adagrad (accumulators from
+ *   0: a += g g; p -= lr g / (sqrt(a) + eps)).
+ * side 0: one row per node, C = E columns; side 1: one row per edge, C = N.
+ * 1 <= dim <= 512 (HGX_EUNSUP above); HGX_EUNSUP with a message when the
+ * weights, accumulators and gradients with the smallest chunk of the logit
+ * block do not fit into the free device memory.
+ *
+ * A sample is a pair (row, drop): the target is 1 / n on the n columns of
+ * the row, the input the same (drop = -1) or 1 / (n - 1) on the row without
+ * its column `drop`. hgx_ae_step runs one train_on_batch on an explicit
+ * sample list (one Adagrad step, *loss = the batch mean); HGX_EINVAL for a
+ * row outside the side, a drop that is not a column of its row, a drop on a
+ * row of one column, or an empty list. A batch's n x C logit block is
+ * processed in chunks of rows (tuning "ae_chunk_rows"), gradients summed
+ * over the chunks in a fixed order.
+ *
+ * hgx_ae_draw: the samples of the listed rows in list order, per row the
+ * unperturbed sample and then, for a row of n > 1 columns, min(n,
+ * samples_per_idx) distinct columns of it in ascending order: all of them
+ * when n <= samples_per_idx, else a uniform subset from the library's
+ * counter-based generator keyed by (seed, row, epoch) alone. *n is the sample
+ * count; row_out / drop_out (n entries each) may be NULL to ask for it.
+ *
+ * hgx_ae_fit: `epochs` passes over every row of the side; per epoch the rows
+ * of perms[epoch] (a permutation of [0, R), HGX_EINVAL otherwise; NULL: the
+ * library shuffles by sorting counter-based keys of (seed, epoch)) are split
+ * into s = max(1, R / idx_per_batch) sections as numpy.array_split does (the
+ * first R mod s hold one row more) and every section is one batch of the
+ * samples hgx_ae_draw(seed, epoch) gives for it. Every batch is queued on
+ * the context's stream without waiting for the previous one; batch_loss
+ * (epochs x s floats) and *n_batches are written at the end. The weights
+ * after hgx_ae_fit are bit for bit those of the same hgx_ae_draw /
+ * hgx_ae_step calls made one by one.
+ *
+ * hgx_ae_set_weights / _get_weights: the flat float32 layout W1 (C x dim),
+ * b1 (dim), W2 (dim x C), b2 (C), row-major; a set restarts the
+ * accumulators (a new engine holds zeros). hgx_ae_encode: relu(x W1 + b1)
+ * of the unperturbed input of every listed row, out n x dim.
+ * hgx_ae_last_stats: of the last hgx_ae_step or hgx_ae_fit, the device time
+ * (ms, HIP events), the samples and batches trained and the algorithmic
+ * flops, 6 M C dim per batch of M samples. */
+typedef struct hgx_ae hgx_ae;
+int hgx_ae_create(hgx_ctx *ctx, int side, int dim, hgx_ae **out);
+int hgx_ae_destroy(hgx_ae *a);
+int hgx_ae_set_weights(hgx_ae *a, const float *flat);
+int hgx_ae_get_weights(hgx_ae *a, float *flat);
+int hgx_ae_draw(hgx_ae *a, int64_t n_idx, const int32_t *rows,
+                int samples_per_idx, uint64_t seed, int epoch, int64_t *n,
+                int32_t *row_out, int32_t *drop_out);
+int hgx_ae_step(hgx_ae *a, int64_t n, const int32_t *row, const int32_t *drop,
+                float lr, float eps, float *loss);
+int hgx_ae_fit(hgx_ae *a, int epochs, int idx_per_batch, int samples_per_idx,
+               float lr, float eps, uint64_t seed, const int64_t *perms,
+               float *batch_loss, int *n_batches);
+int hgx_ae_encode(hgx_ae *a, int64_t n, const int32_t *rows, float *out);
+int hgx_ae_last_stats(const hgx_ae *a, double *ms, int64_t *samples,
+                      int64_t *batches, double *flops);
 
 /* ---- host utilities (bench / test data; not reference entry points) --- *
  * Power-law synthetic incidence of SURVEY.md §8(d) (C4/C5): node degree
