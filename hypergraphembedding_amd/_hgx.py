@@ -287,7 +287,8 @@ class Context:
   def set_tuning(self, key, value):
     """Pick between exact implementations (hgx_set_tuning): sample_reject_w,
     sample_mode3, sample_mode3_shift, sample_mode3_shift_e, train_fused,
-    train_lanes, train_tb, train_wave_pair (1 one record on two waves, 0 off,
+    train_lanes, train_tb, train_wave_pair (1 one record on two waves, 3 on
+    four waves with 2 records per workgroup where padded d = 128, 0 off,
     -1 per geometry), train_prep_overlap, train_prep_cus, alg_long, alg_ks,
     alg_push, mlp_fuse_head, mlp_prefetch, mlp_wgrad_split, svc_lds_m,
     ae_chunk_rows, stream_cus."""

@@ -139,8 +139,9 @@ extern "C" int hgx_set_tuning(hgx_ctx *ctx, const char *key, int64_t value) {
               "train_tb must be 0, 128, 256 or 512");
     t.train_tb = (int)value;
   } else if (k == "train_wave_pair") {
-    HGX_CHECK(ctx, value >= -1 && value <= 1, HGX_EINVAL,
-              "train_wave_pair must be -1, 0 or 1");
+    // (2 was the quad form's 4-record geometry: measured slower, not built)
+    HGX_CHECK(ctx, (value >= -1 && value <= 1) || value == 3, HGX_EINVAL,
+              "train_wave_pair must be -1, 0, 1 or 3");
     t.train_wave_pair = (int)value;
   } else if (k == "alg_long") {
     HGX_CHECK(ctx, value == 0 || (value >= 64 && value <= (1 << 20)), HGX_EINVAL,

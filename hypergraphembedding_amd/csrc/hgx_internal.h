@@ -56,9 +56,10 @@ struct Tuning {
   // trainer step workgroup size (0 auto; 128 / 256 at 32 lanes, 256 / 512 at
   // 64 lanes x float2; other values fall back to the geometry's default)
   int train_tb = 0;
-  // trainer step at 64 lanes per record: one record on two waves (node half,
-  // edge half), 512 threads = 4 records per workgroup. -1 per geometry, 0 off,
-  // 1 on
+  // trainer step at 64 lanes per record: 1 one record on two waves (node half,
+  // edge half), 512 threads = 4 records per workgroup; 3 one record on four
+  // waves (each half on a head and a list wave), 512 threads = 2 records per
+  // workgroup, float2 rows. -1 per geometry, 0 off
   int train_wave_pair = -1;
   // alg-dist: long-row threshold (0: kLongRow) and coordinate row width
   // (0: round_up(k + 1, 4))

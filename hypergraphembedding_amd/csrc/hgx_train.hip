@@ -119,12 +119,21 @@ void step_fns_pair(int loss, KStepFn *kf, KFlushFn &kfl) {
                     : train_step<64, VW, 5, 2, 512, true, true>;
   kfl = train_flush<64 * VW / 4>;
 }
-// the paired-wave form's default per row width (interleaved A/B)
-constexpr int kPairDefault128 = 1, kPairDefault256 = 1;
+// the quad form: one record on four waves, 2 records per 512-thread
+// workgroup, float2 rows (see train_step_quad)
+void step_fns_quad(int loss, KStepFn *kf, KFlushFn &kfl) {
+  kf[0] = loss == 0 ? train_step_q<2, 5, 1, false, 2> : train_step_q<2, 5, 2, false, 2>;
+  kf[1] = loss == 0 ? train_step_q<2, 5, 1, true, 2> : train_step_q<2, 5, 2, true, 2>;
+  kfl = train_flush<32>;
+}
+// the default form per row width: 1 paired, 3 quad (interleaved A/B,
+// DESIGN 4.1)
+constexpr int kPairDefault128 = 3, kPairDefault256 = 1;
 // lanes = the tuning (0 auto, 32 or 64 lanes per record where dp = 128);
 // sets sl (the step's lanes per record), tb, rpb (records per workgroup) and
-// the kernels. pair = the tuning (-1 per geometry): at 64 lanes per record the
-// paired-wave form, 512 threads for 4 records.
+// the kernels. pair = the tuning (-1 per geometry): at 64 lanes per record 1
+// the paired-wave form, 512 threads for 4 records; 3 the quad form, 512
+// threads for 2 records (float2 rows; at float4 rows the paired form).
 bool pick_step(int L, int VPL, int K, int loss, int act, int lanes, int pair, int &sl,
                int &tb, int &rpb, KStepFn *kf, KFlushFn &kfl) {
   if (VPL != 1 || K != 5 || loss != act) return false;
@@ -136,7 +145,14 @@ bool pick_step(int L, int VPL, int K, int loss, int act, int lanes, int pair, in
   sl = L * 4 / vw;
   // (an explicit train_tb keeps the one-wave form it names)
   const int pair_auto = tb != 0 ? 0 : vw == 2 ? kPairDefault128 : kPairDefault256;
-  if (sl == 64 && (pair < 0 ? pair_auto : pair)) {
+  const int form = pair < 0 ? pair_auto : pair;
+  if (sl == 64 && vw == 2 && form == 3) {
+    tb = 512;
+    rpb = 2;
+    step_fns_quad(loss, kf, kfl);
+    return true;
+  }
+  if (sl == 64 && form) {
     tb = 512;
     rpb = 4;
     if (vw == 2) step_fns_pair<2>(loss, kf, kfl);

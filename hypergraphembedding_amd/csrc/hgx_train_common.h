@@ -23,7 +23,7 @@ static constexpr int g_tab = 0;
 #endif
 
 // diagnostic phase trace (HGX_TRAIN_TRACE=<file>, timing experiments only):
-// wave 0 of every workgroup stamps s_memrealtime (100 MHz) at phase ends
+// one wave of every workgroup stamps s_memrealtime (100 MHz) at phase ends
 // for the first g_trace_nb batches; slots [batch][kernel][block < 1024][8].
 // Diagnostic builds only: in a release build the trace pointer is a
 // compile-time null, so the step's prologue has no dependent scalar load of a
@@ -43,12 +43,20 @@ static constexpr int g_trace_nb = 0;
       var = __builtin_amdgcn_s_memrealtime();                       \
     }                                                               \
   } while (0)
+// `who`: the one thread of the workgroup whose stamps are kept. The step
+// passes the first lane of its last record group's (head) wave: placement
+// deals the records without neighbour lists first, so wave 0 always holds one
+// of those and its stamps under-report the waves that set the batch time.
 __device__ __forceinline__ void trace_put(int gb, int kern, int nst,
-                                          const unsigned long long *t) {
-  if (g_trace && threadIdx.x == 0 && gb < g_trace_nb && blockIdx.x < 1024) {
+                                          const unsigned long long *t, bool who) {
+  if (g_trace && who && gb < g_trace_nb && blockIdx.x < 1024) {
     unsigned long long *q = g_trace + (((size_t)gb * 2 + kern) * 1024 + blockIdx.x) * 8;
     for (int i = 0; i < nst; i++) q[i] = t[i];
   }
+}
+__device__ __forceinline__ void trace_put(int gb, int kern, int nst,
+                                          const unsigned long long *t) {
+  trace_put(gb, kern, nst, t, threadIdx.x == 0);
 }
 
 struct TrainArgs {

@@ -1,5 +1,5 @@
 // Trainer kernels, deferred-row step: fixed point, SV<>, the row-0 helpers,
-// train_step, train_step_pair and train_flush.
+// train_step, train_step_pair, train_step_quad and train_flush.
 #pragma once
 #include "hgx_train_split.h"
 
@@ -667,7 +667,376 @@ __device__ __forceinline__ void train_step_pair(const TrainArgs &a, int cb, int 
   }
   if (__any(bad) && !g_tab && lane == 0) atomicOr(a.ovf, 1);
   HGX_STAMP(ts[6]);
-  trace_put(gb, 0, 7, ts);
+  trace_put(gb, 0, 7, ts, threadIdx.x == (NW - 2) * L);
+}
+
+// The quad form of the step (64 lanes per record, 256 RPB threads): each table
+// half of the paired form on two waves, waves 4g .. 4g + 3 of the workgroup
+// the node head, node list, edge head and edge list wave of record g. Of the
+// half's own slots j = 0 (H), 1 (O), 2 + k (Tk) the head wave has H, O and
+// T0 .. T(KH-1), the list wave the other KL list rows, and H's table row to
+// dot them with. Both fold pending slots of what they read (every reader of
+// a deferred row computes the same bits), reduce their dots (the reduction
+// tree is per value), and meet at ONE workgroup barrier: the 1 + K dots of
+// both halves (s_zx) and the list wave's post-fold rows (s_t) go through LDS,
+// then every wave of the record runs the paired form's scalar head math from
+// the twelve dots itself. The head wave runs the whole hub chain and the
+// whole row-0 sum of its table in emit order (lists, H, O; a list slot's term
+// is d[k] H), adds it and (node head) stores the loss word; each wave emits
+// its own slots with the paired form's emit classes.
+// A row repeated within the record (kSLocal) sums in LDS in emit order, so a
+// half with such a slot among the list wave's is not split: its head wave runs
+// the paired form's whole 7-slot program (role kQFull) and its list wave only
+// reaches the barriers (kQIdle); a wave-uniform test on the codes both waves
+// hold. Flush slot 0 rides on the list wave of its table, flush slots 1..
+// on waves 1..3 of the record. Same placed buffers, placed for RPB = 2: 128
+// workgroups of 512 threads, half the paired form's gathers, stores and
+// atomics per CU. Float2 rows (padded d = 128) only: the 4-record,
+// 1024-thread geometry measured slower than the paired form at both row
+// widths, and at float4 rows the padding row's gradient is a
+// float sum over the workgroup's records, bit-identical to the other forms
+// only over their four.
+enum { kQFull = 0, kQHead = 1, kQList = 2, kQIdle = 3 };
+template <int ROLE, int J, int JH>
+struct QRole {
+  static constexpr unsigned all = (1u << J) - 1, head = (1u << JH) - 1;
+  // slots whose table row the wave reads / slots it emits
+  static constexpr unsigned pm = ROLE == kQFull   ? all
+                                 : ROLE == kQHead ? head
+                                 : ROLE == kQList ? ((all & ~head) | 1u)
+                                                  : 0u;
+  static constexpr unsigned om = ROLE == kQList ? (all & ~head) : pm;
+};
+template <int V>
+struct QC {
+  static constexpr int value = V;
+};
+template <int VW, int K, int MODE, bool MULTI, int RPB>
+__device__ __forceinline__ void train_step_quad(const TrainArgs &a, int cb, int gb, int nb,
+                                                int q) {
+  constexpr int L = 64, NW = 4 * RPB, TB = NW * L, R = 4 + 2 * K, J = 2 + K;
+  constexpr int KH = 1, JH = 2 + KH, KL = K - KH;  // list rows of the head / list wave
+  constexpr int NZ = 1 + K;                        // head dots of one half
+  using S = SV<VW>;
+  using V = typename S::T;
+  static_assert(R + kWX <= 32, "slot and batch words fit the first 32 lanes");
+  static_assert((1 + KH) % 2 == 0 && KL % 2 == 0 && NZ % 2 == 0,
+                "the head dots reduce in groups of four, then two");
+  static_assert(kFX <= 4, "flush slots 1.. on waves 1..3 of the record");
+  // (every record adds its own row-0 sums: no per-workgroup float sum)
+  static_assert(HGX_TRAIN_R0EARLY && VW == 2, "the quad form is built for early row-0 sums");
+  __shared__ V s_gl[RPB][R][L];  // gradients of local (one-record) rows
+  __shared__ V s_r0[2][L];
+  __shared__ V s_t[RPB][2][KL][L];  // the list waves' rows, for the hub chains
+  __shared__ __attribute__((aligned(16))) float s_zx[RPB][2][8];  // z, z0 .. z(K-1) per half
+  unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (g_trace) ts[0] = __builtin_amdgcn_s_memrealtime();
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / L), lane = threadIdx.x % L;
+  const int grp = wave >> 2, half = (wave >> 1) & 1, sub = wave & 1;  // sub 1: the list wave
+  const bool edge = half;
+  const int NBF = gridDim.x, RW = a.RW;
+  const int par = q % 3, ppar = (q + 2) % 3, zpar = (q + 1) % 3;
+  // round trip 1: as the paired form, all four waves loading their record's
+  // words; the padding-row loads by waves 0 and 1 (node / edge table's row 0)
+  const size_t gi = ((size_t)cb * NBF + blockIdx.x) * RPB + grp;
+  const int *ri = a.pidx + gi * RW;
+  const unsigned *rc = a.pcode + gi * RW;
+  const float *yt = a.ptgt + gi * 3;
+  const int sl = lane < RW ? lane : 0;
+  const int rv = ri[sl];
+  const int cv = (int)rc[sl];
+  const int tv = __float_as_int(yt[lane < 3 ? lane : 0]);
+  Row0Loads<L, VW> r0l;
+  if (wave < 2) row0_issue<L, VW>(a, q, r0l);
+  int row[J], frow[kFX];
+  unsigned code[J], fcode[kFX];
+  const int sH = edge ? 3 : 0, sO = edge ? 1 : 2, sT = 4 + half * K;
+  auto slot_of = [&](int j) { return j == 0 ? sH : j == 1 ? sO : sT + j - 2; };
+#pragma unroll
+  for (int j = 0; j < J; j++) {
+    row[j] = __builtin_amdgcn_readlane(rv, slot_of(j));
+    code[j] = (unsigned)__builtin_amdgcn_readlane(cv, slot_of(j));
+  }
+#pragma unroll
+  for (int f = 0; f < kFX; f++) {
+    frow[f] = __builtin_amdgcn_readlane(rv, R + f);
+    fcode[f] = (unsigned)__builtin_amdgcn_readlane(cv, R + f);
+  }
+  const int nfo = __builtin_amdgcn_readlane(rv, R + kFX);
+  const int zc = __builtin_amdgcn_readlane(rv, R + kFX + 1);
+  const float yt0 = __int_as_float(__builtin_amdgcn_readlane(tv, 0));
+  const float yt1 = __int_as_float(__builtin_amdgcn_readlane(tv, 1));
+  const float yt2 = __int_as_float(__builtin_amdgcn_readlane(tv, 2));
+  HGX_STAMP(ts[1]);
+  const int nval = min(max(nb - (int)blockIdx.x + NBF - 1, 0) / NBF, RPB);
+  const bool has = grp < nval;
+  // the half is split unless a list-wave slot repeats a row of the record
+  unsigned lc = 0;
+#pragma unroll
+  for (int j = JH; j < J; j++) lc |= code[j];
+  const bool split = !(lc & kSLocal);
+  const int role = !has ? kQIdle : sub == 0 ? (split ? kQHead : kQFull) : (split ? kQList : kQIdle);
+  // (always_inline: a role body left out of line keeps the rows in scratch)
+  auto by_role = [&](auto &&f) __attribute__((always_inline)) {
+    if (role == kQHead) f(QC<kQHead>{});
+    else if (role == kQList) f(QC<kQList>{});
+    else if (role == kQFull) f(QC<kQFull>{});
+  };
+  int bad = 0;
+  if (nval > 0) {
+    // round trip 2: this wave's rows of its table
+    V *Tw = reinterpret_cast<V *>(edge ? a.etab : a.ntab);
+    V *Aw = reinterpret_cast<V *>(edge ? a.eacc : a.nacc);
+    const V *T = Tw, *Ac = Aw;
+    V Pv[J], Av[J];
+    by_role([&](auto rl) __attribute__((always_inline)) {
+      using QR = QRole<decltype(rl)::value, J, JH>;
+      bool lists = false;
+#pragma unroll
+      for (int j = 2; j < J; j++)
+        if ((QR::pm >> j) & 1u) lists |= row[j] != 0;
+#pragma unroll
+      for (int j = 0; j < J; j++) {
+        if (!((QR::pm >> j) & 1u)) continue;
+        // a padding head slot (its value comes from s_r0 below) / no list
+        // gathers; accumulator rows only where the wave owns the update
+        if (j < 2 ? row[j] != 0 : lists) {
+          const int arow = (code[j] & kSOwn) ? row[j] : 0;
+          Pv[j] = T[(size_t)row[j] * L + lane];
+          if ((QR::om >> j) & 1u) Av[j] = Ac[(size_t)arow * L + lane];
+        } else if (j < 2) {
+          Pv[j] = S::zero();
+          Av[j] = S::zero();
+        }
+      }
+    });
+    // flush slot 0 rides on the same round trip, on the list wave of its table
+    const bool fmine = sub == 1 && frow[0] != 0 && (bool)(fcode[0] & kFEdge) == edge;
+    V fp, fa;
+    typename S::Fx fg;
+    if (fmine) {
+      const int mf = (fcode[0] >> kDefBits) & kDefMask;
+      fp = sh_row<L, VW>(a, ppar, mf, 0)[lane];
+      fa = sh_row<L, VW>(a, ppar, mf, 1)[lane];
+      fg = S::ldfix(gacc_row<L, VW>(a, ppar, mf), lane);
+    }
+    if (wave < 2) {
+      V p0 = r0l.rp, a0 = r0l.ra;
+      S::pin(p0);
+      S::pin(a0);
+      row0_finish<L, VW>(a, q, r0l, p0, a0);
+      s_r0[wave][lane] = p0;
+      if (blockIdx.x == 0) {
+        st_row(&sh_row<L, VW>(a, par, wave, 0)[lane], p0);
+        st_row(&sh_row<L, VW>(a, par, wave, 1)[lane], a0);
+      }
+    }
+    __syncthreads();  // s_r0
+    HGX_STAMP(ts[2]);
+    if (has && fmine) {
+      fold<VW>(fp, fa, fg, a.lr, a.eps);
+      st_row(&Tw[(size_t)frow[0] * L + lane], fp);
+      st_row(&Aw[(size_t)frow[0] * L + lane], fa);
+    }
+    const int act = MODE == 1 ? 0 : 1;
+    const int lossk = MODE == 1 ? 0 : 1;
+    by_role([&](auto rl) __attribute__((always_inline)) {
+      using QR = QRole<decltype(rl)::value, J, JH>;
+      constexpr int ROLE = decltype(rl)::value;
+      // pending slots among the rows this wave read
+      unsigned pm = 0;
+#pragma unroll
+      for (int j = 0; j < J; j++)
+        if (((QR::pm >> j) & 1u) && (code[j] & kSPend)) pm |= 1u << j;
+      auto fold_pass = [&]() __attribute__((always_inline)) {
+        if (pm == 0) return;
+        const int ps = __builtin_ctz(pm);
+        unsigned cd = 0;
+#pragma unroll
+        for (int j = 0; j < J; j++)
+          if (j == ps) cd = code[j];
+        const unsigned mp = (cd >> kDefBits) & kDefMask;
+        const typename S::Fx gg = S::ldfix(gacc_row<L, VW>(a, ppar, mp), lane);
+        V pp = sh_row<L, VW>(a, ppar, mp, 0)[lane], aa = sh_row<L, VW>(a, ppar, mp, 1)[lane];
+        unsigned wm = 0;
+#pragma unroll
+        for (int j = 0; j < J; j++)
+          if (((code[j] >> kDefBits) & kDefMask) == mp) wm |= 1u << j;
+        wm &= pm;
+        fold<VW>(pp, aa, gg, a.lr, a.eps);
+#pragma unroll
+        for (int j = 0; j < J; j++)
+          if (((QR::pm >> j) & 1u) && ((wm >> j) & 1u)) {
+            Pv[j] = pp;
+            Av[j] = aa;
+          }
+        pm &= ~wm;
+      };
+      fold_pass();
+      if (MULTI) {
+        fold_pass();
+        if (pm != 0) {
+#pragma unroll
+          for (int j = 0; j < J; j++) {
+            if (!((QR::pm >> j) & 1u) || !((pm >> j) & 1u)) continue;
+            const int mp = (code[j] >> kDefBits) & kDefMask;
+            const typename S::Fx gg = S::ldfix(gacc_row<L, VW>(a, ppar, mp), lane);
+            V pp = sh_row<L, VW>(a, ppar, mp, 0)[lane], aa = sh_row<L, VW>(a, ppar, mp, 1)[lane];
+            fold<VW>(pp, aa, gg, a.lr, a.eps);
+            Pv[j] = pp;
+            Av[j] = aa;
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < J; j++)
+        if (((QR::pm >> j) & 1u) && row[j] == 0) Pv[j] = s_r0[half][lane];
+      // forward: this wave's dots reduced together, to s_zx[.][0] (z = H.O)
+      // and s_zx[.][1 + k] (zk = Tk.H)
+      constexpr int K0 = ROLE == kQList ? KH : 0, K1 = ROLE == kQHead ? KH : K;
+      constexpr int Z0 = ROLE == kQList ? 0 : 1, NQ = Z0 + K1 - K0;
+      float zz[NQ];
+      if (Z0) zz[0] = S::dot(Pv[0], Pv[1]);
+#pragma unroll
+      for (int k = K0; k < K1; k++) zz[Z0 + k - K0] = S::dot(Pv[2 + k], Pv[0]);
+      hgx::wave_allreduce_sum_n<NQ>(zz);
+      if (lane == 0) {
+        if (Z0) s_zx[grp][half][0] = zz[0];
+#pragma unroll
+        for (int k = K0; k < K1; k++) s_zx[grp][half][1 + k] = zz[Z0 + k - K0];
+      }
+      if (ROLE == kQList) {
+#pragma unroll
+        for (int k = KH; k < K; k++) s_t[grp][half][k - KH][lane] = Pv[2 + k];
+      }
+    });
+    __syncthreads();  // s_zx, s_t (reached by every wave, with a record or not)
+    by_role([&](auto rl) __attribute__((always_inline)) {
+      using QR = QRole<decltype(rl)::value, J, JH>;
+      constexpr int ROLE = decltype(rl)::value;
+      // the paired form's head math, on every wave of the record
+      const float inv_b = 1.0f / (float)nb;
+      const float *zo = s_zx[grp][half], *zp = s_zx[grp][half ^ 1];
+      const float zh = zo[0], yh = act_f(act, zh);
+      float zk[K], sk[K], PQo = 0.f, PQp = 0.f;
+#pragma unroll
+      for (int k = 0; k < K; k++) {
+        zk[k] = zo[1 + k];
+        sk[k] = act_f(act, zk[k]);
+        PQo += sk[k];
+      }
+      PQo = PQo / (float)K;
+#pragma unroll
+      for (int k = 0; k < K; k++) PQp += act_f(act, zp[1 + k]);
+      PQp = PQp / (float)K;
+      const float P = edge ? PQp : PQo, Q = edge ? PQo : PQp;
+      const float y3 = mul_nc(P, Q);
+      float lh, l3, gh, g3, lrec = 0.f;
+      head_loss_nc(lossk, yh, edge ? yt1 : yt0, lh, gh);
+      head_loss_nc(lossk, y3, yt2, l3, g3);
+      if (!edge && ROLE != kQList) {
+        const float y1 = yh, y2 = act_f(act, zp[0]);
+        float l1, l2, g1, g2;
+        head_loss_nc(lossk, y1, yt0, l1, g1);
+        head_loss_nc(lossk, y2, yt1, l2, g2);
+        lrec = add_nc(add_nc(l1, l2), l3);
+      }
+      HGX_STAMP(ts[3]);
+      gh *= inv_b;
+      g3 *= inv_b;
+      const float dz = gh * act_d_nc(act, zh, yh);
+      // dP = g3 Q / K on the node waves, dQ = g3 P / K on the edge waves
+      const float dk = g3 * (edge ? P : Q) / (float)K;
+      const V &H = Pv[0], &O = Pv[1];
+      auto emit = [&](int j, V g) __attribute__((always_inline)) {
+        const unsigned cd = code[j];
+        if (row[j] == 0) {
+          // (in the head wave's row-0 sum)
+        } else if (cd & kSLocal) {
+          V *acc = &s_gl[grp][cd & 15u][lane];
+          if (cd & kSOwn) {
+            V pv = Pv[j], av = Av[j];
+            S::adagrad(pv, av, S::add(*acc, g), a.lr, a.eps);
+            st_row(&Tw[(size_t)row[j] * L + lane], pv);
+            st_row(&Aw[(size_t)row[j] * L + lane], av);
+          } else {
+            *acc = (cd & kSFirst) ? g : S::add(*acc, g);
+          }
+        } else if (cd & kSShared) {
+          const int m = cd & kDefMask;
+          S::addfix(gacc_row<L, VW>(a, par, m), lane, g, bad);
+          if (cd & kSOwn) {
+            st_row(&sh_row<L, VW>(a, par, m, 0)[lane], Pv[j]);
+            st_row(&sh_row<L, VW>(a, par, m, 1)[lane], Av[j]);
+          }
+        } else {
+          V pv = Pv[j], av = Av[j];
+          S::adagrad(pv, av, g, a.lr, a.eps);
+          st_row(&Tw[(size_t)row[j] * L + lane], pv);
+          st_row(&Aw[(size_t)row[j] * L + lane], av);
+        }
+      };
+      float d[K];
+#pragma unroll
+      for (int k = 0; k < K; k++) d[k] = dk * act_d_nc(act, zk[k], sk[k]);
+      if (ROLE != kQList) {
+        if (ROLE == kQHead) {
+#pragma unroll
+          for (int k = KH; k < K; k++) Pv[2 + k] = s_t[grp][half][k - KH][lane];
+        }
+        // the hub chain and the table's row-0 sum, in emit order
+        V gH = S::fma(dz, O, S::zero()), zT = S::zero();
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+          gH = S::fma(d[k], Pv[2 + k], gH);
+          if (row[2 + k] == 0) zT = S::add(zT, S::fma(d[k], H, S::zero()));
+        }
+        if (row[0] == 0) zT = S::add(zT, gH);
+        if (row[1] == 0) zT = S::add(zT, S::fma(dz, H, S::zero()));
+        const int slot = (blockIdx.x * RPB + grp) % R0S<VW * L>::n;
+        S::addfix(r0_row<L, VW>(a, par, slot, half), lane, zT, bad);
+        if (!edge && lane == 0)
+          a.lossbuf[(size_t)gb * a.lstride + blockIdx.x * RPB + grp] = lrec;
+#pragma unroll
+        for (int k = 0; k < K; k++)
+          if ((QR::om >> (2 + k)) & 1u) emit(2 + k, S::fma(d[k], H, S::zero()));
+        emit(0, gH);
+        emit(1, S::fma(dz, H, S::zero()));
+      } else {
+#pragma unroll
+        for (int k = KH; k < K; k++) emit(2 + k, S::fma(d[k], H, S::zero()));
+      }
+      HGX_STAMP(ts[4]);
+    });
+    // flush slots 1.., on waves 1..3 of the record
+#pragma unroll
+    for (int f = 1; f < kFX; f++)
+      if (frow[f] != 0 && f == (wave & 3)) flush_slot<L, VW>(a, ppar, frow[f], fcode[f], lane);
+  }
+  HGX_STAMP(ts[5]);
+  // flush overflow list and the zeroing loops, over all waves
+  for (int e = blockIdx.x * NW + wave; e < nfo; e += NBF * NW) {
+    const int2 en = a.pfo[(size_t)cb * a.Mmax + e];
+    flush_row<L, VW>(a, ppar, en.x, en.y, lane);
+  }
+  {
+    longlong2 *z = reinterpret_cast<longlong2 *>(gacc_row<L, VW>(a, zpar, 2));
+    const int tot = zc * (VW / 2) * L;
+    for (int i = blockIdx.x * TB + threadIdx.x; i < tot; i += NBF * TB)
+      z[i] = make_longlong2(0, 0);
+    longlong2 *zr = reinterpret_cast<longlong2 *>(r0_row<L, VW>(a, zpar, 0, 0));
+    for (int i = blockIdx.x * TB + threadIdx.x; i < R0S<VW * L>::n * VW * L; i += NBF * TB)
+      zr[i] = make_longlong2(0, 0);
+  }
+  if (__any(bad) && !g_tab && lane == 0) atomicOr(a.ovf, 1);
+  HGX_STAMP(ts[6]);
+  trace_put(gb, 0, 7, ts, threadIdx.x == (NW - 4) * L);
+}
+
+template <int VW, int KMAX, int MODE, bool MULTI, int RPB>
+__global__ __launch_bounds__(256 * RPB) void train_step_q(TrainArgs a, int cb, int gb, int nb,
+                                                          int q) {
+  train_step_quad<VW, KMAX, MODE, MULTI, RPB>(a, cb, gb, nb, q);
 }
 
 // PAIR: the paired-wave form above (L = 64, TB = 512, 4 records per workgroup)
@@ -1092,7 +1461,7 @@ __global__ __launch_bounds__(TB) void train_step(TrainArgs a, int cb, int gb, in
   // (timing ablations compute wrong values: no overflow verdict for them)
   if (__any(bad) && !g_tab && (threadIdx.x & 63) == 0) atomicOr(a.ovf, 1);
   HGX_STAMP(ts[6]);
-  trace_put(gb, 0, 7, ts);
+  trace_put(gb, 0, 7, ts, threadIdx.x == (RPB - 1) * L);
 }
 
 // End of an epoch: the last batch's deferred rows folded into the tables

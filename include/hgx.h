@@ -81,9 +81,12 @@ int hgx_mem_info(hgx_ctx *ctx, int64_t *free_bytes, int64_t *total_bytes);
  *                      256): 1 one record on two waves of a 512-thread
  *                      workgroup (the node wave owns the node-table slots,
  *                      the edge wave the edge-table slots; still 4 records
- *                      per workgroup; overrides train_tb), 0 one wave per
- *                      record, -1 per geometry where train_tb is 0 (default);
- *                      bit-identical
+ *                      per workgroup; overrides train_tb), 3 one record on
+ *                      four waves (each table half on a head and a list
+ *                      wave), 2 records per 512-thread workgroup (padded
+ *                      d = 128; at 256 the same as 1), 0 one wave per
+ *                      record, -1 per geometry where train_tb is 0
+ *                      (default); bit-identical
  *   "alg_long"         alg-dist long-row threshold (0 = 512, else >= 64)
  *   "alg_ks"           alg-dist coordinate row width in floats (0 = auto:
  *                      round_up(k + 1, 4), widened from 12 to 16 floats

@@ -1,6 +1,8 @@
 """Phase trace of the trainer kernels (HGX_TRAIN_TRACE): per batch, the
 K1/K2 spans, inter-kernel gaps and per-workgroup phase durations from
-s_memrealtime stamps (10 ns ticks). Diagnostic only."""
+s_memrealtime stamps (10 ns ticks). Diagnostic only.
+
+  python tools/trace_train.py [d] [n | hobe] [ENV=V+ENV=V | -] [train_wave_pair]"""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -9,7 +11,8 @@ from hypergraphembedding_amd import _hgx
 d = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 hobe = len(sys.argv) > 2 and sys.argv[2] == "hobe"  # the C3 HOBE stream
 n = int(sys.argv[2]) if len(sys.argv) > 2 and not hobe else 400_000
-extra = dict(kv.split("=") for kv in sys.argv[3].split("+")) if len(sys.argv) > 3 else {}
+extra = (dict(kv.split("=") for kv in sys.argv[3].split("+"))
+         if len(sys.argv) > 3 and sys.argv[3] != "-" else {})
 rs = np.random.RandomState(0)
 N, E, K = 100000, 50000, 5
 R = 4 + 2 * K
@@ -24,6 +27,8 @@ idx[m2, 4 + K:] = rs.randint(1, E + 1, (m2.sum(), K))
 tgt = np.zeros((n, 3), np.float32)
 tgt[np.arange(n), kind] = rs.uniform(0, 1, n)
 ctx = _hgx.Context(0)
+if len(sys.argv) > 4:
+  ctx.set_tuning("train_wave_pair", int(sys.argv[4]))
 if hobe:
   from hypergraphembedding_amd.synthetic import random_hypergraph
   inc = random_hypergraph(seed=0)
@@ -43,7 +48,7 @@ path = "gpurun_out/trace.bin" if os.path.isdir("gpurun_out") else "/tmp/trace.bi
 os.environ["HGX_TRAIN_TRACE"] = path
 ctx.train(batch=256, max_epochs=1, loss=1, act=1, min_delta=-1e30)
 ms, rec, bat = ctx.train_stats()
-print(f"{extra} {ms * 1e3 / bat:.2f} us/batch (traced run)")
+print(f"{extra} {ms * 1e3 / bat:.2f} us/batch (traced run), step geometry {ctx.train_step_geometry()}")
 t = np.fromfile(path, np.uint64).reshape(256, 2, 1024, 8).astype(np.int64)
 print("path (fused, split):", ctx.train_path_stats())
 if ctx.train_path_stats()[0] > 0:
