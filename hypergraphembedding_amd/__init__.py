@@ -45,6 +45,8 @@ from .embedding import (COMBINATION_OPTIONS, DEBUG_SUMMARY_OPTIONS,
 from .svd import EmbedRandom, EmbedSvd, svd_incidence
 from .nmf import EmbedNMF, nmf_incidence
 from .auto_encoder import EmbedAutoEncoder, auto_encoder_incidence
+from .node2vec import (EmbedNode2VecBipartide, EmbedNode2VecClique,
+                       node2vec_incidence)
 
 __all__ = [
     # proto
@@ -58,6 +60,8 @@ __all__ = [
     # comparison baselines (reference embedding.py:110-162)
     "EmbedSvd", "EmbedRandom", "svd_incidence", "EmbedNMF", "nmf_incidence",
     "EmbedAutoEncoder", "auto_encoder_incidence",
+    # node2vec baselines (reference embedding.py:165-261)
+    "EmbedNode2VecBipartide", "EmbedNode2VecClique", "node2vec_incidence",
     # hot-path pieces
     "BooleanSamples", "AlgebraicDistanceSamples", "SamplesToModelInput",
     "SimilarityRecord", "UniformWeight", "WeightByNeighborhood",

@@ -176,6 +176,18 @@ SIGNATURES = {
                           _pint]),
     "hgx_ae_encode": (_int, [_vp, _i64, _vp, _vp]),
     "hgx_ae_last_stats": (_int, [_vp, _pdbl, _pi64, _pi64, _pdbl]),
+    "hgx_n2v_create": (_int, [_vp, _int, _int, ctypes.POINTER(_vp)]),
+    "hgx_n2v_destroy": (_int, [_vp]),
+    "hgx_n2v_walks": (_int, [_vp, _i64, _vp, _vp, _int, ctypes.c_double, _u64,
+                             _vp]),
+    "hgx_n2v_counts": (_int, [_vp, _vp]),
+    "hgx_n2v_set_vocab": (_int, [_vp, _vp, _vp]),
+    "hgx_n2v_set_vectors": (_int, [_vp, _vp, _vp]),
+    "hgx_n2v_get_vectors": (_int, [_vp, _vp, _vp]),
+    "hgx_n2v_train": (_int, [_vp, _i64, _int, _vp, _int, _int, _int, _f32,
+                             _f32, _u64, _int]),
+    "hgx_n2v_last_stats": (_int, [_vp, _pdbl, _pdbl, _pi64, _pi64, _pi64,
+                                  _pi64, _pi64]),
     "hgx_pyrandom_sample_missing": (_int, [_vp, _i32, _i32, _vp, _vp, _i64,
                                            _vp, _vp, _pi64]),
     "hgx_pyrandom_remove_connections": (_int, [_vp, _i64, _vp, _vp, _vp, _vp,
@@ -291,7 +303,7 @@ class Context:
     four waves with 2 records per workgroup where padded d = 128, 0 off,
     -1 per geometry), train_prep_overlap, train_prep_cus, alg_long, alg_ks,
     alg_push, mlp_fuse_head, mlp_prefetch, mlp_wgrad_split, svc_lds_m,
-    ae_chunk_rows, stream_cus."""
+    ae_chunk_rows, n2v_expand_w, n2v_chunk_walks, stream_cus."""
     self._chk(lib().hgx_set_tuning(self.h, key.encode(), int(value)))
 
   # ---- incidence ----
@@ -1073,6 +1085,95 @@ class Ae:
                                           ctypes.byref(fl)))
     return {"ms": ms.value, "samples": sm.value, "batches": bt.value,
             "flops": fl.value}
+
+
+class N2v:
+  """One hgx_n2v engine (include/hgx.h, node2vec baselines) on a Context
+  whose incidence is uploaded: the walks, the vocabulary tables and the two
+  V x dim tables of the skip-gram trainer on the device, for the bipartite
+  (0) or the clique (1) graph. This is the device backend of
+  node2vec.node2vec_incidence."""
+
+  BIPARTITE, CLIQUE = 0, 1
+
+  def __init__(self, ctx, graph, dim):
+    self.ctx, self.graph, self.dim = ctx, int(graph), int(dim)
+    h = _vp()
+    ctx._chk(lib().hgx_n2v_create(ctx.h, self.graph, self.dim, ctypes.byref(h)))
+    self.h = h
+    self.V = ctx.inc.N if self.graph else ctx.inc.N + ctx.inc.E
+    ctx._engines.add(self)
+
+  def close(self):
+    if getattr(self, "h", None):
+      lib().hgx_n2v_destroy(self.h)
+      self.h = None
+
+  def __del__(self):
+    try:
+      self.close()
+    except Exception:
+      pass
+
+  def __enter__(self):
+    return self
+
+  def __exit__(self, *exc):
+    self.close()
+
+  def walks(self, passes, sources, walk_length, p, seed, copy=True):
+    """One walk per (pass, source), kept on the device; the (n, walk_length)
+    int32 host copy unless ``copy`` is False (hgx_n2v_walks)."""
+    ps, sr = _c(passes, np.int32).ravel(), _c(sources, np.int32).ravel()
+    assert ps.size == sr.size
+    out = np.empty((sr.size, int(walk_length)), np.int32) if copy else None
+    self.ctx._chk(lib().hgx_n2v_walks(self.h, sr.size, _ptr(ps), _ptr(sr),
+                                      int(walk_length), float(p),
+                                      int(seed) & (2**64 - 1), _ptr(out)))
+    return out
+
+  def counts(self):
+    """Occurrences of every vertex in the resident walks (int64)."""
+    out = np.empty(self.V, np.int32)
+    self.ctx._chk(lib().hgx_n2v_counts(self.h, _ptr(out)))
+    return out.astype(np.int64)
+
+  def set_vocab(self, keep, cum):
+    keep, cum = _c(keep, np.uint32).ravel(), _c(cum, np.int32).ravel()
+    assert keep.size == cum.size == self.V
+    self.ctx._chk(lib().hgx_n2v_set_vocab(self.h, _ptr(keep), _ptr(cum)))
+
+  def set_vectors(self, syn0, syn1=None):
+    s0 = _c(syn0, np.float32).reshape(self.V, self.dim)
+    s1 = None if syn1 is None else _c(syn1, np.float32).reshape(self.V, self.dim)
+    self.ctx._chk(lib().hgx_n2v_set_vectors(self.h, _ptr(s0), _ptr(s1)))
+
+  def get_vectors(self):
+    s0 = np.empty((self.V, self.dim), np.float32)
+    s1 = np.empty((self.V, self.dim), np.float32)
+    self.ctx._chk(lib().hgx_n2v_get_vectors(self.h, _ptr(s0), _ptr(s1)))
+    return s0, s1
+
+  def train(self, walks=None, *, window=3, negative=5, epochs=5, alpha=0.025,
+            min_alpha=1e-4, seed=0, concurrent=True):
+    """Skip-gram with negative sampling over the resident walks, or over the
+    explicit (n, walk_length) ``walks`` (hgx_n2v_train)."""
+    w = None if walks is None else _c(walks, np.int32)
+    n, L = (0, 0) if w is None else w.shape
+    self.ctx._chk(lib().hgx_n2v_train(self.h, n, L, _ptr(w), int(window),
+                                      int(negative), int(epochs), alpha,
+                                      min_alpha, int(seed) & (2**64 - 1),
+                                      1 if concurrent else 0))
+
+  def stats(self):
+    wm, tm = ctypes.c_double(), ctypes.c_double()
+    v = [ctypes.c_int64() for _ in range(5)]
+    self.ctx._chk(lib().hgx_n2v_last_stats(self.h, ctypes.byref(wm),
+                                           ctypes.byref(tm),
+                                           *[ctypes.byref(x) for x in v]))
+    return {"walk_ms": wm.value, "train_ms": tm.value, "walks": v[0].value,
+            "words": v[1].value, "pairs": v[2].value,
+            "expand_steps": v[3].value, "reject_steps": v[4].value}
 
 
 # ---- host utilities (no context, no device) --------------------------------

@@ -99,6 +99,11 @@ struct Tuning {
   // auto-encoder: rows of one chunk of a batch's logit block (rounded up to
   // a multiple of 32; 0: sized from the free device memory)
   int ae_chunk_rows = 0;
+  // node2vec clique walks: rows of at most this many paths expand, longer
+  // ones sample by rejection (0: always rejection)
+  int n2v_expand_w = 256;
+  // node2vec concurrent trainer: walks per launch (0: from the vertex count)
+  int n2v_chunk_walks = 0;
 };
 
 struct hgx_ctx {

@@ -13,9 +13,10 @@ device -> Keras-semantics fit -> rows idx+1 copied into the proto.
 ``EmbedRandom`` and ``EmbedSvd`` (110-140) live in svd.py; "RANDOM" is
 registered, "SVD" is bound by the integrator, and so
 is "NMF" to ``EmbedNMF`` (143-162, nmf.py) and "AUTO_ENCODER" to
-``EmbedAutoEncoder`` (auto_encoder.py). The reference's node2vec methods are
-outside this package: their keys raise like the reference's
-``method_not_supported`` (419-420).
+``EmbedAutoEncoder`` (auto_encoder.py). ``EmbedNode2VecBipartide`` and
+``EmbedNode2VecClique`` (165-261) live in node2vec.py; the integrator binds
+the six "N2V*" keys to them with ``walk_length`` 3, 5 and 7, and here those
+keys raise like the reference's ``method_not_supported`` (419-420).
 """
 
 import logging
@@ -34,6 +35,8 @@ from .proto import HypergraphEmbedding
 from .runtime import check_rng, get_context, numpy_seed, numpy_state_seed
 from .auto_encoder import EmbedAutoEncoder, auto_encoder_incidence
 from .nmf import EmbedNMF, nmf_incidence
+from .node2vec import (EmbedNode2VecBipartide, EmbedNode2VecClique,
+                       node2vec_incidence)
 from .svd import EmbedRandom, EmbedSvd
 
 log = logging.getLogger()
@@ -581,7 +584,8 @@ EMBEDDING_OPTIONS = {
     # (svd.py), EmbedNMF (nmf.py) and EmbedAutoEncoder (auto_encoder.py)
     # exist; a reference-side integrator binds "SVD", "NMF" and
     # "AUTO_ENCODER" to them, this registry keeps the
-    # three keys unsupported
+    # three keys unsupported; the same holds for the six "N2V*" keys and
+    # EmbedNode2VecBipartide / EmbedNode2VecClique (node2vec.py)
     "SVD": method_not_supported,
     "RANDOM": EmbedRandom,
     "NMF": method_not_supported,
@@ -609,4 +613,6 @@ __all__ = ["Embed", "EMBEDDING_OPTIONS", "DEBUG_SUMMARY_OPTIONS",
            "EmbedHg2vNeighborhoodWeightedJaccard",
            "CombineEmbeddingsViaConcatenation", "method_not_supported",
            "EmbedSvd", "EmbedRandom", "EmbedNMF", "nmf_incidence",
-           "EmbedAutoEncoder", "auto_encoder_incidence"]
+           "EmbedAutoEncoder", "auto_encoder_incidence",
+           "EmbedNode2VecBipartide", "EmbedNode2VecClique",
+           "node2vec_incidence"]

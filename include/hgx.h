@@ -120,6 +120,13 @@ int hgx_mem_info(hgx_ctx *ctx, int64_t *free_bytes, int64_t *total_bytes);
  *   "ae_chunk_rows"    auto-encoder: rows of one chunk of a batch's logit
  *                      block, rounded up to a multiple of 32 (0 = sized from
  *                      the free device memory, default; at most 65536)
+ *   "n2v_expand_w"     node2vec clique walks: a row with at most this many
+ *                      paths draws its distinct neighbour by expansion, a
+ *                      longer one by rejection (default 256; 0 = always
+ *                      rejection; the same distribution)
+ *   "n2v_chunk_walks"  node2vec concurrent trainer: walks per launch (0 =
+ *                      about a quarter of the vertex count, in [64, 4096],
+ *                      default; at most 65536)
  * Unknown keys and out-of-range values -> HGX_EINVAL. */
 int hgx_set_tuning(hgx_ctx *ctx, const char *key, int64_t value);
 
@@ -683,6 +690,71 @@ int hgx_ae_fit(hgx_ae *a, int epochs, int idx_per_batch, int samples_per_idx,
 int hgx_ae_encode(hgx_ae *a, int64_t n, const int32_t *rows, float *out);
 int hgx_ae_last_stats(const hgx_ae *a, double *ms, int64_t *samples,
                       int64_t *batches, double *flops);
+
+/* ---- node2vec baselines ---------------------------------------------------- *
+ * The device half of EmbedNode2VecBipartide / EmbedNode2VecClique (reference
+ * embedding.py:165-261; the node2vec package's walks and gensim's skip-gram
+ * negative-sampling trainer restated) on the incidence uploaded
+ * before hgx_n2v_create (HGX_ESTATE without one, or after it was replaced).
+ * graph 0, bipartite: node v is vertex v, edge e is vertex N + e, V = N + E.
+ * graph 1, clique: the vertices are the nodes, V = N, u ~ v iff u != v and
+ * they share an edge, every distinct neighbour with weight 1; the graph is
+ * never materialised. 1 <= dim <= 512 (HGX_EUNSUP above, or when the two
+ * V x dim tables do not fit).
+ *
+ * hgx_n2v_walks: one walk of walk_length vertices (the source included;
+ * at most 128, HGX_EUNSUP above) per listed (pass, source). Step 1 is uniform
+ * over the neighbours; from step 2 the previous vertex has weight 1 / p and
+ * every other neighbour 1 (0 < p <= 1; p = 0 is HGX_EZERODIV, anything else
+ * HGX_EINVAL; q = 1). Every draw is keyed by (seed, pass, source, step), so a
+ * walk does not depend on the other entries of the list. HGX_EINVAL for a
+ * source without a neighbour (a node of the clique graph that shares no edge
+ * of two nodes, any zero-degree row of the bipartite graph). The walks stay
+ * on the device for hgx_n2v_counts and hgx_n2v_train; walks_out (n x
+ * walk_length, NULL to skip) receives a copy. The clique draw expands rows
+ * of at most "n2v_expand_w" paths and samples longer ones by rejection.
+ *
+ * hgx_n2v_counts: occurrences of every vertex in the resident walks (V
+ * entries). hgx_n2v_set_vocab: keep[w], the 32-bit threshold of word w's
+ * subsampling (a word stays iff keep[w] > a uniform draw below 2^32 - 1), and
+ * cum, the non-decreasing cumulative table of the negatives (a negative is
+ * the first w with cum[w] >= a uniform draw below cum[V - 1]).
+ *
+ * hgx_n2v_train: `epochs` passes of skip-gram with `negative` (at most 8)
+ * negatives over the resident walks, or over `walks` (n_walks x walk_length
+ * vertices, which then become the resident ones) when it is not NULL. Per
+ * kept word i of a walk and reduced window, per kept word j of the window:
+ * l1 = syn0[w_j] held fixed; for t = w_i (label 1), then each negative
+ * (label 0, one equal to w_i skipped), in order: x = l1 . syn1[t], skipped
+ * when |x| >= 6, g = (label - 1 / (1 + exp(-x))) alpha, neu += g syn1[t],
+ * syn1[t] += g l1; then syn0[w_j] += neu. alpha falls linearly from `alpha`
+ * to `min_alpha` over the epochs x n_walks walks. concurrent 0: one wave
+ * trains the walks in order (reproducible bit for bit). concurrent 1: the
+ * walks of a chunk ("n2v_chunk_walks") train at once on a wave each, every
+ * update a float atomic add; same draws, results differ in the last bits
+ * from run to run.
+ *
+ * hgx_n2v_set_vectors / _get_vectors: V x dim float32 row-major; a NULL syn1
+ * sets zeros / is not read back. hgx_n2v_last_stats: device time of the last
+ * hgx_n2v_walks and hgx_n2v_train (ms, HIP events), the walks, kept words and
+ * pairs of the last hgx_n2v_train, and the clique steps of the last
+ * hgx_n2v_walks drawn by expansion and by rejection. */
+typedef struct hgx_n2v hgx_n2v;
+int hgx_n2v_create(hgx_ctx *ctx, int graph, int dim, hgx_n2v **out);
+int hgx_n2v_destroy(hgx_n2v *n);
+int hgx_n2v_walks(hgx_n2v *n, int64_t n_src, const int32_t *pass,
+                  const int32_t *source, int walk_length, double p,
+                  uint64_t seed, int32_t *walks_out);
+int hgx_n2v_counts(hgx_n2v *n, int32_t *counts);
+int hgx_n2v_set_vocab(hgx_n2v *n, const uint32_t *keep, const int32_t *cum);
+int hgx_n2v_set_vectors(hgx_n2v *n, const float *syn0, const float *syn1);
+int hgx_n2v_get_vectors(hgx_n2v *n, float *syn0, float *syn1);
+int hgx_n2v_train(hgx_n2v *n, int64_t n_walks, int walk_length,
+                  const int32_t *walks, int window, int negative, int epochs,
+                  float alpha, float min_alpha, uint64_t seed, int concurrent);
+int hgx_n2v_last_stats(const hgx_n2v *n, double *walk_ms, double *train_ms,
+                       int64_t *walks, int64_t *words, int64_t *pairs,
+                       int64_t *expand_steps, int64_t *reject_steps);
 
 /* ---- host utilities (bench / test data; not reference entry points) --- *
  * Power-law synthetic incidence of SURVEY.md §8(d) (C4/C5): node degree
