@@ -47,6 +47,7 @@ from .nmf import EmbedNMF, nmf_incidence
 from .auto_encoder import EmbedAutoEncoder, auto_encoder_incidence
 from .node2vec import (EmbedNode2VecBipartide, EmbedNode2VecClique,
                        node2vec_incidence)
+from .deepwalk import EmbedDeepWalk, deepwalk_incidence
 
 __all__ = [
     # proto
@@ -62,6 +63,8 @@ __all__ = [
     "EmbedAutoEncoder", "auto_encoder_incidence",
     # node2vec baselines (reference embedding.py:165-261)
     "EmbedNode2VecBipartide", "EmbedNode2VecClique", "node2vec_incidence",
+    # DeepWalk baseline (the "deepwalk" key)
+    "EmbedDeepWalk", "deepwalk_incidence",
     # hot-path pieces
     "BooleanSamples", "AlgebraicDistanceSamples", "SamplesToModelInput",
     "SimilarityRecord", "UniformWeight", "WeightByNeighborhood",

@@ -188,6 +188,10 @@ SIGNATURES = {
                              _f32, _u64, _int]),
     "hgx_n2v_last_stats": (_int, [_vp, _pdbl, _pdbl, _pi64, _pi64, _pi64,
                                   _pi64, _pi64]),
+    "hgx_n2v_set_tree": (_int, [_vp, _vp, _vp, _vp]),
+    "hgx_n2v_train_hs": (_int, [_vp, _i64, _int, _vp, _int, _int, _f32, _f32,
+                                _u64, _int]),
+    "hgx_n2v_last_hs_stats": (_int, [_vp, _pi64]),
     "hgx_pyrandom_sample_missing": (_int, [_vp, _i32, _i32, _vp, _vp, _i64,
                                            _vp, _vp, _pi64]),
     "hgx_pyrandom_remove_connections": (_int, [_vp, _i64, _vp, _vp, _vp, _vp,
@@ -303,7 +307,7 @@ class Context:
     four waves with 2 records per workgroup where padded d = 128, 0 off,
     -1 per geometry), train_prep_overlap, train_prep_cus, alg_long, alg_ks,
     alg_push, mlp_fuse_head, mlp_prefetch, mlp_wgrad_split, svc_lds_m,
-    ae_chunk_rows, n2v_expand_w, n2v_chunk_walks, stream_cus."""
+    ae_chunk_rows, n2v_expand_w, n2v_chunk_walks, dw_hot_levels, stream_cus."""
     self._chk(lib().hgx_set_tuning(self.h, key.encode(), int(value)))
 
   # ---- incidence ----
@@ -1165,15 +1169,37 @@ class N2v:
                                       min_alpha, int(seed) & (2**64 - 1),
                                       1 if concurrent else 0))
 
+  def set_tree(self, ptr, point, code):
+    """The Huffman paths of deepwalk.huffman_tree (hgx_n2v_set_tree)."""
+    ptr, point = _c(ptr, np.int32).ravel(), _c(point, np.int32).ravel()
+    code = _c(code, np.uint8).ravel()
+    assert ptr.size == self.V + 1
+    assert point.size == code.size and (ptr[-1] < 0 or point.size >= ptr[-1])
+    self.ctx._chk(lib().hgx_n2v_set_tree(self.h, _ptr(ptr), _ptr(point),
+                                         _ptr(code)))
+
+  def train_hs(self, walks=None, *, window=5, epochs=5, alpha=0.025,
+               min_alpha=1e-4, seed=0, concurrent=True):
+    """Skip-gram with hierarchical softmax over the resident walks, or over
+    the explicit (n, walk_length) ``walks`` (hgx_n2v_train_hs)."""
+    w = None if walks is None else _c(walks, np.int32)
+    n, L = (0, 0) if w is None else w.shape
+    self.ctx._chk(lib().hgx_n2v_train_hs(self.h, n, L, _ptr(w), int(window),
+                                         int(epochs), alpha, min_alpha,
+                                         int(seed) & (2**64 - 1),
+                                         1 if concurrent else 0))
+
   def stats(self):
     wm, tm = ctypes.c_double(), ctypes.c_double()
-    v = [ctypes.c_int64() for _ in range(5)]
+    v = [ctypes.c_int64() for _ in range(6)]
     self.ctx._chk(lib().hgx_n2v_last_stats(self.h, ctypes.byref(wm),
                                            ctypes.byref(tm),
-                                           *[ctypes.byref(x) for x in v]))
+                                           *[ctypes.byref(x) for x in v[:5]]))
+    self.ctx._chk(lib().hgx_n2v_last_hs_stats(self.h, ctypes.byref(v[5])))
     return {"walk_ms": wm.value, "train_ms": tm.value, "walks": v[0].value,
             "words": v[1].value, "pairs": v[2].value,
-            "expand_steps": v[3].value, "reject_steps": v[4].value}
+            "expand_steps": v[3].value, "reject_steps": v[4].value,
+            "path_nodes": v[5].value}
 
 
 # ---- host utilities (no context, no device) --------------------------------

@@ -104,6 +104,10 @@ struct Tuning {
   int n2v_expand_w = 256;
   // node2vec concurrent trainer: walks per launch (0: from the vertex count)
   int n2v_chunk_walks = 0;
+  // DeepWalk concurrent trainer: path positions (tree levels from the root)
+  // whose rows a workgroup sums in LDS, 0 to 6 (0: every update a global
+  // atomic). 6 measured fastest at every row width
+  int dw_hot_levels = 6;
 };
 
 struct hgx_ctx {

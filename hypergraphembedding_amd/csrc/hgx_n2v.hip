@@ -14,8 +14,12 @@
 //   n2v_hist         count[w] = occurrences of vertex w in the walks
 //   n2v_train        SGNS over the walks: one wave per walk, lane l holds
 //                    columns l + 64 q of a row (d padded to 64, 128, 256, 512)
+//   n2v_train_hs     DeepWalk's trainer, skip-gram with hierarchical softmax
+//                    over the same walks, keeps and windows: per pair the
+//                    inner nodes of the output word's Huffman path, root
+//                    first, their rows of syn1 loaded kHsBatch per round trip
 //
-// The trainer has two modes. Sequential: one wave trains the walks in corpus
+// Either trainer has two modes. Sequential: one wave trains the walks in corpus
 // order with plain loads and stores; this is the definition of the result.
 // Concurrent: a chunk of walks per launch, one wave each; every update is a
 // float atomic add without return (lossless), every row read is an
@@ -28,6 +32,16 @@
 //            counter (position i << 7 | position j) << 4 | slot
 //            slot 0 the keep draw of position i, 1 its window reduction,
 //            2 + k negative k of the pair (input word at j, output word at i)
+//
+// Hot rows of the hierarchical-softmax trainer. Every pair
+// updates the root's row of syn1, half of them each child's, and so on: sent
+// as global atomics these adds would queue on a handful of rows. In concurrent
+// mode the inner nodes at path positions below T = "dw_hot_levels" (a heap
+// slot from the code bits above them: at most 2^T - 1 = 63 rows) are summed
+// per workgroup in LDS: a hot row is read as its global value plus the
+// workgroup's sum, its update is an LDS float add, and after a workgroup
+// barrier each non-zero sum goes to memory as one atomic row add. A wave sees
+// its own updates at once, the other workgroups at the next launch.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -47,6 +61,10 @@ constexpr int kMaxT = 1 + kMaxNeg;
 constexpr int kMaxTry = 1 << 16;  // proposals per clique step before the step gives up
 constexpr int kStatSlots = 64;
 constexpr int kSeqWalks = 8192;  // walks per launch of the sequential trainer
+constexpr int kMaxCode = 64;     // longest Huffman path (word2vec's C code: 40)
+constexpr int kMaxHotLevels = 6; // path positions summed in LDS: 2^6 - 1 = 63 rows
+constexpr int kMaxHotRows = (1 << kMaxHotLevels) - 1;
+constexpr int kHsBatch = 8;      // rows of a path loaded per round trip
 
 __host__ __device__ inline uint64_t walk_ctr(int step, int it, int slot) {
   return ((uint64_t)step << 24) | ((uint64_t)it << 2) | (uint64_t)slot;
@@ -238,7 +256,12 @@ struct TrainArgs {
   const int *walks;
   const unsigned *keep;
   const int *cum;
-  unsigned long long *stats;  // kStatSlots x {words, pairs}
+  unsigned long long *stats;  // kStatSlots x {words, pairs}, then kStatSlots path nodes
+  // hierarchical softmax: vertex v's path is point / code [ptr[v], ptr[v + 1]),
+  // root first; hot_row[s] the inner node of heap slot s (-1: none)
+  const int *ptr, *point, *hot_row;
+  const uint8_t *code;
+  int hot_levels;
   int dp, L, V, window, negative, epochs;
   int n_walks;
   uint32_t cum_last;
@@ -314,18 +337,19 @@ __device__ __forceinline__ void train_pair(const TrainArgs &A, int lane, int wj,
   }
 }
 
-// One walk on one wave. kw / kb: the kept words and (position | span << 8),
-// span = window - b the reduced window; ng: the negatives of one output
-// position's pairs, drawn by all lanes at once (a binary search of the
-// cumulative table each) so that no pair waits on one.
-template <int NPL, bool CONC>
-__device__ __forceinline__ void train_walk(const TrainArgs &A, int lane, int ep, int w,
-                                           volatile int *kw, volatile int *kb, volatile int *ng) {
-  const uint64_t key = hgx::rand64_key(A.seed, ((uint64_t)(uint32_t)ep << 32) | (uint32_t)w);
+// alpha of walk w in epoch ep: linear in the walk's global index
+__device__ __forceinline__ float walk_alpha(const TrainArgs &A, int ep, int w) {
   const double gidx = (double)ep * (double)A.n_walks + (double)w;
   const double tot = (double)A.epochs * (double)A.n_walks;
   const double a = A.alpha - (A.alpha - A.min_alpha) * gidx / tot;
-  const float alpha = (float)(a > A.min_alpha ? a : A.min_alpha);
+  return (float)(a > A.min_alpha ? a : A.min_alpha);
+}
+
+// The kept words of walk w, compacted in walk order: kw the words, kb
+// (position | span << 8), span = window - b the reduced window. Returns their
+// number; the wave may read kw / kb after it.
+__device__ __forceinline__ int walk_keeps(const TrainArgs &A, int lane, uint64_t key, int w,
+                                          volatile int *kw, volatile int *kb) {
   int nk = 0;
   for (int h = 0; h < 2; h++) {
     const int pos = lane + 64 * h;
@@ -347,6 +371,18 @@ __device__ __forceinline__ void train_walk(const TrainArgs &A, int lane, int ep,
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  return nk;
+}
+
+// One walk on one wave. ng: the negatives of one output position's pairs,
+// drawn by all lanes at once (a binary search of the cumulative table each)
+// so that no pair waits on one.
+template <int NPL, bool CONC>
+__device__ __forceinline__ void train_walk(const TrainArgs &A, int lane, int ep, int w,
+                                           volatile int *kw, volatile int *kb, volatile int *ng) {
+  const uint64_t key = hgx::rand64_key(A.seed, ((uint64_t)(uint32_t)ep << 32) | (uint32_t)w);
+  const float alpha = walk_alpha(A, ep, w);
+  const int nk = walk_keeps(A, lane, key, w, kw, kb);
   long long pairs = 0;
   for (int i = 0; i < nk; i++) {
     const int wi = __builtin_amdgcn_readfirstlane(kw[i]);
@@ -401,6 +437,170 @@ __global__ __launch_bounds__(256) void n2v_train(TrainArgs A, int ep, int ep1, i
   }
 }
 
+// ---- trainer, hierarchical softmax ------------------------------------------
+// One pair: l1 = syn0[wj] held fixed; the len inner nodes of the output
+// word's path (point / code from pb on), root first, kHsBatch rows per round
+// trip: the rows of a path are distinct and l1 is fixed, so they do not see
+// each other. hot: the workgroup's sums of the hot rows (concurrent mode); the
+// node at position k < hot_levels has heap slot 2^k - 1 + (the code bits above
+// it), and only the first batch holds such positions.
+template <int NPL, bool CONC>
+__device__ __forceinline__ void train_pair_hs(const TrainArgs &A, int lane, int wj, int pb,
+                                              int len, float alpha, float *hot) {
+  static_assert(kMaxHotLevels <= kHsBatch, "the hot positions lie in the first batch");
+  float *r0 = A.syn0 + (size_t)wj * A.dp + lane;
+  float l1[NPL], neu[NPL];
+#pragma unroll
+  for (int q = 0; q < NPL; q++) {
+    l1[q] = row_load<CONC>(r0 + 64 * q);
+    neu[q] = 0.f;
+  }
+  for (int k0 = 0; k0 < len; k0 += kHsBatch) {
+    float r[kHsBatch][NPL], x[kHsBatch];
+    int tg[kHsBatch], cd[kHsBatch], hs[kHsBatch];
+#pragma unroll
+    for (int k = 0; k < kHsBatch; k++) {
+      const bool on = k0 + k < len;
+      tg[k] = on ? A.point[pb + k0 + k] : -1;
+      cd[k] = on ? (int)A.code[pb + k0 + k] : 0;
+      hs[k] = -1;
+      if (on) {
+        const float *s = A.syn1 + (size_t)tg[k] * A.dp + lane;
+#pragma unroll
+        for (int q = 0; q < NPL; q++) r[k][q] = row_load<CONC>(s + 64 * q);
+      }
+    }
+    if (CONC && k0 == 0) {
+      int pre = 0;
+#pragma unroll
+      for (int k = 0; k < kMaxHotLevels; k++) {
+        if (k < A.hot_levels && k < len) {
+          hs[k] = ((1 << k) - 1 + pre) * A.dp + lane;
+#pragma unroll
+          for (int q = 0; q < NPL; q++)
+            r[k][q] += __hip_atomic_load(hot + hs[k] + 64 * q, __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_WORKGROUP);
+          pre = 2 * pre + cd[k];
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kHsBatch; k++) {
+      x[k] = 0.f;
+      if (tg[k] >= 0) {
+#pragma unroll
+        for (int q = 0; q < NPL; q++) x[k] += l1[q] * r[k][q];
+      }
+    }
+    hgx::wave_allreduce_sum_n<kHsBatch>(x);
+#pragma unroll
+    for (int k = 0; k < kHsBatch; k++) {
+      if (tg[k] >= 0 && fabsf(x[k]) < 6.0f) {  // word2vec's MAX_EXP
+        const double sg = 1.0 / (1.0 + exp(-(double)x[k]));
+        const float g = (float)((double)(1 - cd[k]) - sg) * alpha;
+        float *s = A.syn1 + (size_t)tg[k] * A.dp + lane;
+#pragma unroll
+        for (int q = 0; q < NPL; q++) {
+          neu[q] += g * r[k][q];
+          const float dlt = g * l1[q];
+          if (!CONC) s[64 * q] = r[k][q] + dlt;
+          else if (hs[k] >= 0)
+            __hip_atomic_fetch_add(hot + hs[k] + 64 * q, dlt, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+          else unsafeAtomicAdd(s + 64 * q, dlt);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NPL; q++) {
+    if (CONC) unsafeAtomicAdd(r0 + 64 * q, neu[q]);
+    else r0[64 * q] = l1[q] + neu[q];
+  }
+}
+
+// One walk on one wave: train_walk's keeps, windows and pair order, no
+// negatives. A word without a path (it never occurs, or it is the only word)
+// is an output word whose pairs change nothing.
+template <int NPL, bool CONC>
+__device__ __forceinline__ void train_walk_hs(const TrainArgs &A, int lane, int ep, int w,
+                                              volatile int *kw, volatile int *kb, float *hot) {
+  const uint64_t key = hgx::rand64_key(A.seed, ((uint64_t)(uint32_t)ep << 32) | (uint32_t)w);
+  const float alpha = walk_alpha(A, ep, w);
+  const int nk = walk_keeps(A, lane, key, w, kw, kb);
+  long long pairs = 0, nodes = 0;
+  for (int i = 0; i < nk; i++) {
+    const int wi = __builtin_amdgcn_readfirstlane(kw[i]);
+    const int span = __builtin_amdgcn_readfirstlane(kb[i]) >> 8;
+    const int j0 = max(0, i - span), j1 = min(nk - 1, i + span);
+    const int pb = A.ptr[wi], len = A.ptr[wi + 1] - pb;
+    for (int j = j0; j <= j1; j++) {
+      if (j == i) continue;
+      const int wj = __builtin_amdgcn_readfirstlane(kw[j]);
+      train_pair_hs<NPL, CONC>(A, lane, wj, pb, len, alpha, hot);
+      pairs++;
+      nodes += len;
+    }
+  }
+  if (lane == 0) {
+    unsigned long long *st = A.stats + 2 * (w % kStatSlots);
+    atomicAdd(st, (unsigned long long)nk);
+    atomicAdd(st + 1, (unsigned long long)pairs);
+    atomicAdd(A.stats + 2 * kStatSlots + w % kStatSlots, (unsigned long long)nodes);
+  }
+}
+
+// n2v_train's geometry. Concurrent: s_hot (dynamic LDS, (2^hot_levels - 1) x
+// dp floats) starts at zero, the workgroup's four waves add their hot-row
+// deltas into it, and after the barrier wave wv sends the non-zero rows
+// wv, wv + 4, ... to memory, one atomic row add each.
+template <int NPL, bool CONC>
+__global__ __launch_bounds__(256) void n2v_train_hs(TrainArgs A, int ep, int ep1, int w0,
+                                                    int w1) {
+  __shared__ int s_kw[4][kMaxL], s_kb[4][kMaxL];
+  extern __shared__ float s_hot[];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (CONC) {
+    const int n_hot = (1 << A.hot_levels) - 1;
+    for (int i = threadIdx.x; i < n_hot * A.dp; i += 256) s_hot[i] = 0.f;
+    __syncthreads();
+    const int w = w0 + blockIdx.x * 4 + wv;
+    if (w < w1) train_walk_hs<NPL, true>(A, lane, ep, w, s_kw[wv], s_kb[wv], s_hot);
+    __syncthreads();
+    for (int s = wv; s < n_hot; s += 4) {
+      const int row = A.hot_row[s];
+      if (row < 0) continue;
+      float v[NPL];
+      bool nz = false;
+#pragma unroll
+      for (int q = 0; q < NPL; q++) {
+        v[q] = s_hot[s * A.dp + lane + 64 * q];
+        nz |= v[q] != 0.f;
+      }
+      if (__ballot(nz)) {
+        float *g = A.syn1 + (size_t)row * A.dp + lane;
+#pragma unroll
+        for (int q = 0; q < NPL; q++) unsafeAtomicAdd(g + 64 * q, v[q]);
+      }
+    }
+  } else {
+    for (int e = ep; e < ep1; e++)
+      for (int w = w0; w < w1; w++)
+        train_walk_hs<NPL, false>(A, lane, e, w, s_kw[0], s_kb[0], nullptr);
+  }
+}
+
+using TrainFn = void (*)(TrainArgs, int, int, int, int);
+template <bool HS, bool CONC>
+TrainFn train_kernel(int npl) {
+  switch (npl) {
+    case 1: return HS ? n2v_train_hs<1, CONC> : n2v_train<1, CONC>;
+    case 2: return HS ? n2v_train_hs<2, CONC> : n2v_train<2, CONC>;
+    case 4: return HS ? n2v_train_hs<4, CONC> : n2v_train<4, CONC>;
+    default: return HS ? n2v_train_hs<8, CONC> : n2v_train<8, CONC>;
+  }
+}
+
 }  // namespace
 
 struct hgx_n2v {
@@ -409,6 +609,8 @@ struct hgx_n2v {
   uint64_t inc_gen = 0;
   std::vector<int32_t> h_rp_n, h_col_n, h_rp_e;  // host copy: preconditions
   DevBuf syn0, syn1, walks, pass, src, count, keep, cum, stats, pstats;
+  DevBuf ptr, point, code, hot_row;  // the Huffman tree (hgx_n2v_set_tree)
+  bool tree = false;
   int64_t n_walks = 0;  // resident walks
   int L = 0;
   bool vocab = false;
@@ -416,6 +618,7 @@ struct hgx_n2v {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   double walk_ms = 0, train_ms = 0;
   int64_t st_walks = 0, st_words = 0, st_pairs = 0, st_expand = 0, st_reject = 0;
+  int64_t st_path_nodes = 0;  // of the last hgx_n2v_train_hs
 };
 
 namespace {
@@ -454,7 +657,7 @@ extern "C" int hgx_n2v_destroy(hgx_n2v *a) {
   if (!a) return HGX_OK;
   if (a->ctx) hipStreamSynchronize(a->ctx->stream);
   for (DevBuf *b : {&a->syn0, &a->syn1, &a->walks, &a->pass, &a->src, &a->count, &a->keep,
-                    &a->cum, &a->stats, &a->pstats})
+                    &a->cum, &a->stats, &a->pstats, &a->ptr, &a->point, &a->code, &a->hot_row})
     hgx_release(*b);
   for (hipEvent_t e : {a->e0, a->e1})
     if (e) hipEventDestroy(e);
@@ -475,7 +678,7 @@ static int n2v_alloc(hgx_n2v *a) {
   HGX_TRY(hgx_ensure(ctx, a->count, sizeof(int) * (size_t)a->V));
   HGX_TRY(hgx_ensure(ctx, a->keep, sizeof(unsigned) * (size_t)a->V));
   HGX_TRY(hgx_ensure(ctx, a->cum, sizeof(int) * (size_t)a->V));
-  HGX_TRY(hgx_ensure(ctx, a->stats, sizeof(unsigned long long) * 2 * kStatSlots));
+  HGX_TRY(hgx_ensure(ctx, a->stats, sizeof(unsigned long long) * 3 * kStatSlots));
   HGX_TRY(hgx_ensure(ctx, a->pstats, sizeof(unsigned long long) * 2));
   HGX_HIP(ctx, hipMemsetAsync(a->syn0.p, 0, a->syn0.bytes, ctx->stream));
   HGX_HIP(ctx, hipMemsetAsync(a->syn1.p, 0, a->syn1.bytes, ctx->stream));
@@ -674,32 +877,101 @@ extern "C" int hgx_n2v_get_vectors(hgx_n2v *a, float *syn0, float *syn1) {
   return n2v_vectors_io(a, syn0, syn1, false);
 }
 
-extern "C" int hgx_n2v_train(hgx_n2v *a, int64_t n_walks, int walk_length,
-                             const int32_t *walks, int window, int negative, int epochs,
-                             float alpha, float min_alpha, uint64_t seed, int concurrent) {
+extern "C" int hgx_n2v_set_tree(hgx_n2v *a, const int32_t *ptr, const int32_t *point,
+                                const uint8_t *code) {
   if (!a) return HGX_EINVAL;
   hgx_ctx *ctx = a->ctx;
   HGX_TRY(n2v_live(a));
-  HGX_CHECK(ctx, a->vocab, HGX_ESTATE, "hgx_n2v_train before hgx_n2v_set_vocab");
+  HGX_CHECK(ctx, ptr, HGX_EINVAL, "hgx_n2v_set_tree: null ptr");
+  const int V = a->V;
+  HGX_CHECK(ctx, ptr[0] == 0, HGX_EINVAL, "hgx_n2v_set_tree: ptr[0] = %d", ptr[0]);
+  for (int v = 0; v < V; v++) {
+    HGX_CHECK(ctx, ptr[v + 1] >= ptr[v], HGX_EINVAL, "hgx_n2v_set_tree: ptr decreases at %d", v);
+    HGX_CHECK(ctx, ptr[v + 1] - ptr[v] <= kMaxCode, HGX_EUNSUP,
+              "hgx_n2v_set_tree: vertex %d has a path of %d inner nodes, above %d", v,
+              ptr[v + 1] - ptr[v], kMaxCode);
+  }
+  const size_t total = (size_t)ptr[V];
+  HGX_CHECK(ctx, total == 0 || (point && code), HGX_EINVAL, "hgx_n2v_set_tree: null table");
+  // hot[s]: the inner node of heap slot s = 2^j - 1 + (the code bits above
+  // position j), j < kMaxHotLevels. The kernel derives s from the code bits,
+  // so the paths must agree on it; seen[t] = v + 1: t is on v's path already.
+  std::vector<int32_t> hot(kMaxHotRows, -1), seen((size_t)V, 0);
+  for (int v = 0; v < V; v++) {
+    int pre = 0;
+    for (int i = ptr[v], j = 0; i < ptr[v + 1]; i++, j++) {
+      const int t = point[i];
+      HGX_CHECK(ctx, t >= 0 && t < V - 1, HGX_EINVAL,
+                "hgx_n2v_set_tree: inner node %d on vertex %d's path outside [0, %d)", t, v,
+                V - 1);
+      HGX_CHECK(ctx, code[i] <= 1, HGX_EINVAL, "hgx_n2v_set_tree: code %d on vertex %d's path",
+                (int)code[i], v);
+      HGX_CHECK(ctx, seen[t] != v + 1, HGX_EINVAL,
+                "hgx_n2v_set_tree: inner node %d twice on vertex %d's path", t, v);
+      seen[t] = v + 1;
+      if (j < kMaxHotLevels) {
+        const int s = (1 << j) - 1 + pre;
+        HGX_CHECK(ctx, hot[s] < 0 || hot[s] == t, HGX_EINVAL,
+                  "hgx_n2v_set_tree: the paths are not those of one tree (inner nodes %d and %d "
+                  "at position %d under the same code bits)", hot[s], t, j);
+        hot[s] = t;
+        pre = 2 * pre + code[i];
+      }
+    }
+  }
+  for (int s = 0; s < kMaxHotRows; s++)
+    for (int u = 0; u < s; u++)
+      HGX_CHECK(ctx, hot[s] < 0 || hot[s] != hot[u], HGX_EINVAL,
+                "hgx_n2v_set_tree: the paths are not those of one tree (inner node %d under two "
+                "code prefixes)", hot[s]);
+  a->tree = false;
+  HGX_TRY(hgx_ensure(ctx, a->ptr, sizeof(int32_t) * ((size_t)V + 1)));
+  HGX_TRY(hgx_ensure(ctx, a->point, sizeof(int32_t) * std::max<size_t>(total, 1)));
+  HGX_TRY(hgx_ensure(ctx, a->code, std::max<size_t>(total, 1)));
+  HGX_TRY(hgx_ensure(ctx, a->hot_row, sizeof(int32_t) * kMaxHotRows));
+  HGX_HIP(ctx, hipMemcpyAsync(a->ptr.p, ptr, sizeof(int32_t) * ((size_t)V + 1),
+                              hipMemcpyHostToDevice, ctx->stream));
+  if (total) {
+    HGX_HIP(ctx, hipMemcpyAsync(a->point.p, point, sizeof(int32_t) * total,
+                                hipMemcpyHostToDevice, ctx->stream));
+    HGX_HIP(ctx, hipMemcpyAsync(a->code.p, code, total, hipMemcpyHostToDevice, ctx->stream));
+  }
+  HGX_HIP(ctx, hipMemcpyAsync(a->hot_row.p, hot.data(), sizeof(int32_t) * kMaxHotRows,
+                              hipMemcpyHostToDevice, ctx->stream));
+  HGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  a->tree = true;
+  return HGX_OK;
+}
+
+namespace {
+
+// hgx_n2v_train (hs false) and hgx_n2v_train_hs
+int n2v_train_any(hgx_n2v *a, bool hs, int64_t n_walks, int walk_length, const int32_t *walks,
+                  int window, int negative, int epochs, float alpha, float min_alpha,
+                  uint64_t seed, int concurrent) {
+  hgx_ctx *ctx = a->ctx;
+  const char *fn = hs ? "hgx_n2v_train_hs" : "hgx_n2v_train";
+  HGX_TRY(n2v_live(a));
+  HGX_CHECK(ctx, a->vocab, HGX_ESTATE, "%s before hgx_n2v_set_vocab", fn);
+  HGX_CHECK(ctx, !hs || a->tree, HGX_ESTATE, "%s before hgx_n2v_set_tree", fn);
   HGX_CHECK(ctx, window >= 1 && epochs >= 0 && negative >= 0, HGX_EINVAL,
-            "hgx_n2v_train: window %d, epochs %d or negative %d out of range", window, epochs,
-            negative);
-  HGX_CHECK(ctx, negative <= kMaxNeg, HGX_EUNSUP, "hgx_n2v_train: negative %d above %d",
-            negative, kMaxNeg);
-  HGX_CHECK(ctx, concurrent == 0 || concurrent == 1, HGX_EINVAL,
-            "hgx_n2v_train: concurrent %d is not 0 or 1", concurrent);
+            "%s: window %d, epochs %d or negative %d out of range", fn, window, epochs, negative);
+  HGX_CHECK(ctx, negative <= kMaxNeg, HGX_EUNSUP, "%s: negative %d above %d", fn, negative,
+            kMaxNeg);
+  HGX_CHECK(ctx, concurrent == 0 || concurrent == 1, HGX_EINVAL, "%s: concurrent %d is not 0 or 1",
+            fn, concurrent);
   if (walks) {
-    HGX_CHECK(ctx, n_walks >= 1 && walk_length >= 1, HGX_EINVAL,
-              "hgx_n2v_train: %lld walks of length %d", (long long)n_walks, walk_length);
-    HGX_CHECK(ctx, walk_length <= kMaxL, HGX_EUNSUP, "hgx_n2v_train: walk length %d above %d",
+    HGX_CHECK(ctx, n_walks >= 1 && walk_length >= 1, HGX_EINVAL, "%s: %lld walks of length %d",
+              fn, (long long)n_walks, walk_length);
+    HGX_CHECK(ctx, walk_length <= kMaxL, HGX_EUNSUP, "%s: walk length %d above %d", fn,
               walk_length, kMaxL);
     HGX_CHECK(ctx, n_walks * walk_length < (1ll << 31), HGX_EUNSUP,
-              "hgx_n2v_train: %lld walks of %d vertices do not fit 31 bits", (long long)n_walks,
+              "%s: %lld walks of %d vertices do not fit 31 bits", fn, (long long)n_walks,
               walk_length);
     const size_t n = (size_t)n_walks * walk_length;
     for (size_t i = 0; i < n; i++)
       HGX_CHECK(ctx, walks[i] >= 0 && walks[i] < a->V, HGX_EINVAL,
-                "hgx_n2v_train: vertex %d at position %zu outside [0, %d)", walks[i], i, a->V);
+                "%s: vertex %d at position %zu outside [0, %d)", fn, walks[i], i, a->V);
     a->n_walks = 0;
     HGX_TRY(hgx_ensure(ctx, a->walks, sizeof(int) * n));
     HGX_HIP(ctx, hipMemcpyAsync(a->walks.p, walks, sizeof(int) * n, hipMemcpyHostToDevice,
@@ -707,7 +979,7 @@ extern "C" int hgx_n2v_train(hgx_n2v *a, int64_t n_walks, int walk_length,
     a->n_walks = n_walks;
     a->L = walk_length;
   }
-  HGX_CHECK(ctx, a->n_walks > 0, HGX_ESTATE, "hgx_n2v_train without walks");
+  HGX_CHECK(ctx, a->n_walks > 0, HGX_ESTATE, "%s without walks", fn);
   const int nw = (int)a->n_walks;
   TrainArgs A;
   A.syn0 = a->syn0.as<float>();
@@ -716,6 +988,11 @@ extern "C" int hgx_n2v_train(hgx_n2v *a, int64_t n_walks, int walk_length,
   A.keep = a->keep.as<unsigned>();
   A.cum = a->cum.as<int>();
   A.stats = a->stats.as<unsigned long long>();
+  A.ptr = a->ptr.as<int>();
+  A.point = a->point.as<int>();
+  A.hot_row = a->hot_row.as<int>();
+  A.code = a->code.as<uint8_t>();
+  A.hot_levels = hs && concurrent ? ctx->tune.dw_hot_levels : 0;
   A.dp = a->dp;
   A.L = a->L;
   A.V = a->V;
@@ -727,47 +1004,63 @@ extern "C" int hgx_n2v_train(hgx_n2v *a, int64_t n_walks, int walk_length,
   A.seed = seed;
   A.alpha = (double)alpha;
   A.min_alpha = (double)min_alpha;
+  const int npl = a->dp / 64;
+  const TrainFn kern = hs ? (concurrent ? train_kernel<true, true>(npl)
+                                        : train_kernel<true, false>(npl))
+                          : (concurrent ? train_kernel<false, true>(npl)
+                                        : train_kernel<false, false>(npl));
+  // the hot rows' sums: up to 63 x 512 floats = 126 KiB, one workgroup per CU
+  const size_t lds = sizeof(float) * ((1u << A.hot_levels) - 1) * a->dp;
+  if (lds)
+    HGX_HIP(ctx, hipFuncSetAttribute((const void *)kern,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   HGX_HIP(ctx, hipMemsetAsync(a->stats.p, 0, a->stats.bytes, ctx->stream));
   HGX_HIP(ctx, hipEventRecord(a->e0, ctx->stream));
-  const int chunk = chunk_walks(a);
-#define HGX_N2V_TRAIN(N, C, grid, tb, ep, ep1, w0, w1)                                     \
-  hipLaunchKernelGGL((n2v_train<N, C>), dim3(grid), dim3(tb), 0, ctx->stream, A, ep, ep1, w0, w1)
-#define HGX_N2V_BY_DP(C, grid, tb, ep, ep1, w0, w1)                       \
-  switch (a->dp / 64) {                                                   \
-    case 1: HGX_N2V_TRAIN(1, C, grid, tb, ep, ep1, w0, w1); break;        \
-    case 2: HGX_N2V_TRAIN(2, C, grid, tb, ep, ep1, w0, w1); break;        \
-    case 4: HGX_N2V_TRAIN(4, C, grid, tb, ep, ep1, w0, w1); break;        \
-    default: HGX_N2V_TRAIN(8, C, grid, tb, ep, ep1, w0, w1); break;       \
-  }
-  if (epochs > 0) {
-    if (!concurrent) {
-      // one wave, the corpus in order; a launch per kSeqWalks walks keeps
-      // every kernel short (the order, and so every bit, is the same)
-      for (int ep = 0; ep < epochs; ep++)
-        for (int w0 = 0; w0 < nw; w0 += kSeqWalks) {
-          HGX_N2V_BY_DP(false, 1, 64, ep, ep + 1, w0, std::min(nw, w0 + kSeqWalks));
-          HGX_LAUNCH_CHECK(ctx);
-        }
-    } else {
-      for (int ep = 0; ep < epochs; ep++)
-        for (int w0 = 0; w0 < nw; w0 += chunk) {
-          const int w1 = std::min(nw, w0 + chunk);
-          HGX_N2V_BY_DP(true, (w1 - w0 + 3) / 4, 256, ep, ep + 1, w0, w1);
-          HGX_LAUNCH_CHECK(ctx);
-        }
+  // sequential: one wave, the corpus in order; a launch per kSeqWalks walks
+  // keeps every kernel short (the order, and so every bit, is the same).
+  // concurrent: a chunk of walks per launch, four to a workgroup
+  const int step = concurrent ? chunk_walks(a) : kSeqWalks;
+  for (int ep = 0; ep < epochs; ep++)
+    for (int w0 = 0; w0 < nw; w0 += step) {
+      const int w1 = std::min(nw, w0 + step);
+      hipLaunchKernelGGL(kern, dim3(concurrent ? (w1 - w0 + 3) / 4 : 1),
+                         dim3(concurrent ? 256 : 64), lds, ctx->stream, A, ep, ep + 1, w0, w1);
+      HGX_LAUNCH_CHECK(ctx);
     }
-  }
-#undef HGX_N2V_BY_DP
-#undef HGX_N2V_TRAIN
   HGX_TRY(n2v_elapsed(a, &a->train_ms));
-  unsigned long long st[2 * kStatSlots];
+  unsigned long long st[3 * kStatSlots];
   HGX_HIP(ctx, hipMemcpy(st, a->stats.p, sizeof(st), hipMemcpyDeviceToHost));
-  a->st_words = a->st_pairs = 0;
+  a->st_words = a->st_pairs = a->st_path_nodes = 0;
   for (int i = 0; i < kStatSlots; i++) {
     a->st_words += (int64_t)st[2 * i];
     a->st_pairs += (int64_t)st[2 * i + 1];
+    a->st_path_nodes += (int64_t)st[2 * kStatSlots + i];
   }
   a->st_walks = (int64_t)nw * epochs;
+  return HGX_OK;
+}
+
+}  // namespace
+
+extern "C" int hgx_n2v_train(hgx_n2v *a, int64_t n_walks, int walk_length,
+                             const int32_t *walks, int window, int negative, int epochs,
+                             float alpha, float min_alpha, uint64_t seed, int concurrent) {
+  if (!a) return HGX_EINVAL;
+  return n2v_train_any(a, false, n_walks, walk_length, walks, window, negative, epochs, alpha,
+                       min_alpha, seed, concurrent);
+}
+
+extern "C" int hgx_n2v_train_hs(hgx_n2v *a, int64_t n_walks, int walk_length,
+                                const int32_t *walks, int window, int epochs, float alpha,
+                                float min_alpha, uint64_t seed, int concurrent) {
+  if (!a) return HGX_EINVAL;
+  return n2v_train_any(a, true, n_walks, walk_length, walks, window, 0, epochs, alpha, min_alpha,
+                       seed, concurrent);
+}
+
+extern "C" int hgx_n2v_last_hs_stats(const hgx_n2v *a, int64_t *path_nodes) {
+  if (!a) return HGX_EINVAL;
+  if (path_nodes) *path_nodes = a->st_path_nodes;
   return HGX_OK;
 }
 

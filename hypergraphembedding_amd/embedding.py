@@ -17,6 +17,8 @@ is "NMF" to ``EmbedNMF`` (143-162, nmf.py) and "AUTO_ENCODER" to
 ``EmbedNode2VecClique`` (165-261) live in node2vec.py; the integrator binds
 the six "N2V*" keys to them with ``walk_length`` 3, 5 and 7, and here those
 keys raise like the reference's ``method_not_supported`` (419-420).
+``EmbedDeepWalk`` (deepwalk.py) is the device version of the external
+"deepwalk" baseline; the integrator binds that key, here it stays unsupported.
 """
 
 import logging
@@ -37,6 +39,7 @@ from .auto_encoder import EmbedAutoEncoder, auto_encoder_incidence
 from .nmf import EmbedNMF, nmf_incidence
 from .node2vec import (EmbedNode2VecBipartide, EmbedNode2VecClique,
                        node2vec_incidence)
+from .deepwalk import EmbedDeepWalk, deepwalk_incidence
 from .svd import EmbedRandom, EmbedSvd
 
 log = logging.getLogger()
@@ -615,4 +618,4 @@ __all__ = ["Embed", "EMBEDDING_OPTIONS", "DEBUG_SUMMARY_OPTIONS",
            "EmbedSvd", "EmbedRandom", "EmbedNMF", "nmf_incidence",
            "EmbedAutoEncoder", "auto_encoder_incidence",
            "EmbedNode2VecBipartide", "EmbedNode2VecClique",
-           "node2vec_incidence"]
+           "node2vec_incidence", "EmbedDeepWalk", "deepwalk_incidence"]

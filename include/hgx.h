@@ -127,6 +127,12 @@ int hgx_mem_info(hgx_ctx *ctx, int64_t *free_bytes, int64_t *total_bytes);
  *   "n2v_chunk_walks"  node2vec concurrent trainer: walks per launch (0 =
  *                      about a quarter of the vertex count, in [64, 4096],
  *                      default; at most 65536)
+ *   "dw_hot_levels"    DeepWalk concurrent trainer: the inner nodes at the
+ *                      first T positions of a path (T tree levels from the
+ *                      root, at most 2^T - 1 rows) are summed per workgroup in
+ *                      LDS and added to memory once per workgroup; 0 to 6
+ *                      (default 6, measured fastest at every row width), 0 =
+ *                      every update is a global atomic
  * Unknown keys and out-of-range values -> HGX_EINVAL. */
 int hgx_set_tuning(hgx_ctx *ctx, const char *key, int64_t value);
 
@@ -738,7 +744,31 @@ int hgx_ae_last_stats(const hgx_ae *a, double *ms, int64_t *samples,
  * sets zeros / is not read back. hgx_n2v_last_stats: device time of the last
  * hgx_n2v_walks and hgx_n2v_train (ms, HIP events), the walks, kept words and
  * pairs of the last hgx_n2v_train, and the clique steps of the last
- * hgx_n2v_walks drawn by expansion and by rejection. */
+ * hgx_n2v_walks drawn by expansion and by rejection.
+ *
+ * DeepWalk is the same engine at p = 1 with a hierarchical-
+ * softmax trainer. hgx_n2v_set_tree: the Huffman paths, vertex v's inner
+ * nodes point[ptr[v] .. ptr[v + 1]) root first with one code bit each (V + 1,
+ * ptr[V] and ptr[V] entries). Checked on the host before anything is
+ * uploaded: ptr[0] == 0, ptr non-decreasing, every point in [0, V - 1), every
+ * code 0 or 1, no inner node twice on a path, and the paths agree on the
+ * inner node under every code prefix shorter than 6 bits (HGX_EINVAL); a path
+ * longer than 64 is HGX_EUNSUP. A vertex with an empty path is never a target.
+ *
+ * hgx_n2v_train_hs: hgx_n2v_train's walks, keeps, reduced windows, pair order
+ * and alpha schedule (of the vocabulary only keep is read), needs
+ * hgx_n2v_set_vocab and hgx_n2v_set_tree (HGX_ESTATE). Per pair (input word
+ * w_j, output word w_i): l1 = syn0[w_j] held fixed; for each inner node t of
+ * w_i's path, root first, with code bit c: x = l1 . syn1[t], skipped when
+ * |x| >= 6, g = (1 - c - 1 / (1 + exp(-x))) alpha, neu += g syn1[t] (the row
+ * before its update), syn1[t] += g l1; then syn0[w_j] += neu. concurrent 0 is
+ * reproducible bit for bit; concurrent 1 trains a chunk of walks per launch,
+ * and the rows of the first "dw_hot_levels" tree levels are summed per
+ * workgroup on chip: a wave sees its own updates to them at once, the other
+ * workgroups at the next launch; no update is lost.
+ * hgx_n2v_last_stats describes the last run of either trainer;
+ * hgx_n2v_last_hs_stats: the sum of the path lengths over the pairs of the
+ * last hgx_n2v_train_hs (0 after hgx_n2v_train). */
 typedef struct hgx_n2v hgx_n2v;
 int hgx_n2v_create(hgx_ctx *ctx, int graph, int dim, hgx_n2v **out);
 int hgx_n2v_destroy(hgx_n2v *n);
@@ -755,6 +785,12 @@ int hgx_n2v_train(hgx_n2v *n, int64_t n_walks, int walk_length,
 int hgx_n2v_last_stats(const hgx_n2v *n, double *walk_ms, double *train_ms,
                        int64_t *walks, int64_t *words, int64_t *pairs,
                        int64_t *expand_steps, int64_t *reject_steps);
+int hgx_n2v_set_tree(hgx_n2v *n, const int32_t *ptr, const int32_t *point,
+                     const uint8_t *code);
+int hgx_n2v_train_hs(hgx_n2v *n, int64_t n_walks, int walk_length,
+                     const int32_t *walks, int window, int epochs, float alpha,
+                     float min_alpha, uint64_t seed, int concurrent);
+int hgx_n2v_last_hs_stats(const hgx_n2v *n, int64_t *path_nodes);
 
 /* ---- host utilities (bench / test data; not reference entry points) --- *
  * Power-law synthetic incidence of SURVEY.md §8(d) (C4/C5): node degree
