@@ -304,8 +304,9 @@ class Context:
     """Pick between exact implementations (hgx_set_tuning): sample_reject_w,
     sample_mode3, sample_mode3_shift, sample_mode3_shift_e, train_fused,
     train_lanes, train_tb, train_wave_pair (1 one record on two waves, 3 on
-    four waves with 2 records per workgroup where padded d = 128, 0 off,
-    -1 per geometry), train_prep_overlap, train_prep_cus, alg_long, alg_ks,
+    four waves with 2 records per workgroup where padded d = 128, 4 on four
+    waves with 1 record per workgroup there, 0 off, -1 per geometry),
+    train_prep_overlap, train_prep_cus, alg_long, alg_ks,
     alg_push, mlp_fuse_head, mlp_prefetch, mlp_wgrad_split, svc_lds_m,
     ae_chunk_rows, n2v_expand_w, n2v_chunk_walks, dw_hot_levels, stream_cus."""
     self._chk(lib().hgx_set_tuning(self.h, key.encode(), int(value)))

@@ -91,6 +91,7 @@ extern "C" int hgx_destroy(hgx_ctx *ctx) {
     for (DevBuf *b : {&l.seg, &l.off, &l.rows, &l.part}) hgx_release(*b);
   for (hipStream_t &s : ctx->tstream)
     if (s) hipStreamDestroy(s);
+  if (ctx->train_hbrk) hipHostFree(ctx->train_hbrk);
   if (ctx->ev0) hipEventDestroy(ctx->ev0);
   if (ctx->ev1) hipEventDestroy(ctx->ev1);
   if (ctx->own_stream) hipStreamDestroy(ctx->own_stream);
@@ -139,9 +140,10 @@ extern "C" int hgx_set_tuning(hgx_ctx *ctx, const char *key, int64_t value) {
               "train_tb must be 0, 128, 256 or 512");
     t.train_tb = (int)value;
   } else if (k == "train_wave_pair") {
-    // (2 was the quad form's 4-record geometry: measured slower, not built)
-    HGX_CHECK(ctx, (value >= -1 && value <= 1) || value == 3, HGX_EINVAL,
-              "train_wave_pair must be -1, 0, 1 or 3");
+    // (2 was the quad form's 4-record geometry: measured slower, not built;
+    // 4 the quad form at one record per 256-thread workgroup)
+    HGX_CHECK(ctx, (value >= -1 && value <= 1) || value == 3 || value == 4, HGX_EINVAL,
+              "train_wave_pair must be -1, 0, 1, 3 or 4");
     t.train_wave_pair = (int)value;
   } else if (k == "alg_long") {
     HGX_CHECK(ctx, value == 0 || (value >= 64 && value <= (1 << 20)), HGX_EINVAL,

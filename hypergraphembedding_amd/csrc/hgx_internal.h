@@ -59,7 +59,8 @@ struct Tuning {
   // trainer step at 64 lanes per record: 1 one record on two waves (node half,
   // edge half), 512 threads = 4 records per workgroup; 3 one record on four
   // waves (each half on a head and a list wave), 512 threads = 2 records per
-  // workgroup, float2 rows. -1 per geometry, 0 off
+  // workgroup, float2 rows; 4 the same at 256 threads = 1 record per
+  // workgroup. -1 per geometry, 0 off
   int train_wave_pair = -1;
   // alg-dist: long-row threshold (0: kLongRow) and coordinate row width
   // (0: round_up(k + 1, 4))
@@ -236,6 +237,10 @@ struct hgx_ctx {
   // preparation), created for train_prep_cus = tstream_cus
   hipStream_t tstream[2] = {nullptr, nullptr};
   int tstream_cus = -1;
+  // pinned: a chunk's MULTI flags per placed set (trainer forms with a light
+  // step kernel), grown on demand, freed with the context
+  int *train_hbrk = nullptr;
+  size_t train_hbrk_n = 0;
 };
 
 // Diagnostic knobs of the A/B experiments under tools/ (ablations, kernel

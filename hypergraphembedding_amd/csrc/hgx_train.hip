@@ -111,29 +111,42 @@ void step_fns(int loss, KStepFn *kf, KFlushFn &kfl) {
                     : train_step<SL, VW, 5, 2, TB, true>;
   kfl = train_flush<SL * VW / 4>;
 }
+// A merged form (HGX_TRAIN_ONEKERNEL, see hgx_train_step.h) is one kernel:
+// kf[0] == kf[1], which is what tells the driver that it needs no MULTI flags
+// on the host.
+// HGX_TRAIN_CHUNKWAIT=1 (A/B builds): the flag copy and the per-chunk host
+// wait kept for a merged form too (the kernel's cost apart from the driver's)
+#ifndef HGX_TRAIN_CHUNKWAIT
+#define HGX_TRAIN_CHUNKWAIT 0
+#endif
+constexpr bool kMergePair4 = HGX_TRAIN_ONEKERNEL >= 1;  // paired form, float4 rows
+constexpr bool kMergeAll = HGX_TRAIN_ONEKERNEL == 2;    // paired and quad, every width
 template <int VW>
 void step_fns_pair(int loss, KStepFn *kf, KFlushFn &kfl) {
-  kf[0] = loss == 0 ? train_step<64, VW, 5, 1, 512, false, true>
-                    : train_step<64, VW, 5, 2, 512, false, true>;
+  constexpr bool M0 = kMergeAll || (kMergePair4 && VW == 4);  // MULTI of kf[0]
+  kf[0] = loss == 0 ? train_step<64, VW, 5, 1, 512, M0, true>
+                    : train_step<64, VW, 5, 2, 512, M0, true>;
   kf[1] = loss == 0 ? train_step<64, VW, 5, 1, 512, true, true>
                     : train_step<64, VW, 5, 2, 512, true, true>;
   kfl = train_flush<64 * VW / 4>;
 }
-// the quad form: one record on four waves, 2 records per 512-thread
+// the quad form: one record on four waves, RPB records per 256 RPB-thread
 // workgroup, float2 rows (see train_step_quad)
+template <int RPB>
 void step_fns_quad(int loss, KStepFn *kf, KFlushFn &kfl) {
-  kf[0] = loss == 0 ? train_step_q<2, 5, 1, false, 2> : train_step_q<2, 5, 2, false, 2>;
-  kf[1] = loss == 0 ? train_step_q<2, 5, 1, true, 2> : train_step_q<2, 5, 2, true, 2>;
+  kf[0] = loss == 0 ? train_step_q<2, 5, 1, kMergeAll, RPB> : train_step_q<2, 5, 2, kMergeAll, RPB>;
+  kf[1] = loss == 0 ? train_step_q<2, 5, 1, true, RPB> : train_step_q<2, 5, 2, true, RPB>;
   kfl = train_flush<32>;
 }
-// the default form per row width: 1 paired, 3 quad (interleaved A/B,
-// DESIGN 4.1)
-constexpr int kPairDefault128 = 3, kPairDefault256 = 1;
+// the default form per row width: 1 paired, 4 quad at one record per
+// workgroup (interleaved A/B)
+constexpr int kPairDefault128 = 4, kPairDefault256 = 1;
 // lanes = the tuning (0 auto, 32 or 64 lanes per record where dp = 128);
 // sets sl (the step's lanes per record), tb, rpb (records per workgroup) and
 // the kernels. pair = the tuning (-1 per geometry): at 64 lanes per record 1
 // the paired-wave form, 512 threads for 4 records; 3 the quad form, 512
-// threads for 2 records (float2 rows; at float4 rows the paired form).
+// threads for 2 records, 4 the quad form, 256 threads for 1 record (float2
+// rows; at float4 rows the paired form).
 bool pick_step(int L, int VPL, int K, int loss, int act, int lanes, int pair, int &sl,
                int &tb, int &rpb, KStepFn *kf, KFlushFn &kfl) {
   if (VPL != 1 || K != 5 || loss != act) return false;
@@ -149,7 +162,13 @@ bool pick_step(int L, int VPL, int K, int loss, int act, int lanes, int pair, in
   if (sl == 64 && vw == 2 && form == 3) {
     tb = 512;
     rpb = 2;
-    step_fns_quad(loss, kf, kfl);
+    step_fns_quad<2>(loss, kf, kfl);
+    return true;
+  }
+  if (sl == 64 && vw == 2 && form == 4) {
+    tb = 256;
+    rpb = 1;
+    step_fns_quad<1>(loss, kf, kfl);
     return true;
   }
   if (sl == 64 && form) {
@@ -687,8 +706,14 @@ struct EpochPerm {
   }
 };
 
-// One hgx_train call in flight: buffers, streams, events, the pinned MULTI
-// flags and the counters; host resources released on every exit path.
+// One hgx_train call in flight: buffers, streams, events and the counters;
+// host resources released on every exit path. A form with one step kernel
+// (merged: kf[0] == kf[1]) needs nothing from the device inside an epoch: the
+// in-line schedule queues prepare(c + 1) directly behind chunk c's launches
+// (stream order protects the placed set and the skey / sM parities), and a
+// failure surfaces at the epoch's final synchronise, as a step's does. The
+// other forms copy each chunk's MULTI flags into the context's pinned buffer
+// and wait for them, one host wait per chunk.
 struct TrainRun {
   hgx_ctx *ctx;
   const TrainPlan &p;
@@ -706,16 +731,20 @@ struct TrainRun {
   // (overlapped preparation, timing off): chunk c prepared (pev[c]), the
   // epoch's join with ctx->stream (pev[nchunks])
   std::vector<hipEvent_t> bev, pev;
-  int *hbrk = nullptr;  // pinned: the chunk's MULTI flags (train_place) per placed set
+  const bool merged;    // one step kernel: no MULTI flags on the host
+  int *hbrk = nullptr;  // ctx->train_hbrk: the chunk's MULTI flags (train_place) per placed set
   hipError_t flags_err = hipSuccess;  // of the last copy into hbrk
+  // nmulti: train_place's count of flagged batches (ovf[kOvfMulti]) as of the
+  // last finished epoch
   int64_t nfused = 0, nsplit = 0, nmulti = 0;
   double batch_ms = 0.0;
 
-  TrainRun(hgx_ctx *c, const TrainPlan &plan) : ctx(c), p(plan), sst(c->stream), spr(c->stream) {}
+  TrainRun(hgx_ctx *c, const TrainPlan &plan)
+      : ctx(c), p(plan), sst(c->stream), spr(c->stream),
+        merged(plan.fused && plan.kf[0] == plan.kf[1] && !HGX_TRAIN_CHUNKWAIT) {}
   ~TrainRun() {
     for (auto e : bev) if (e) (void)hipEventDestroy(e);
     for (auto e : pev) if (e) (void)hipEventDestroy(e);
-    if (hbrk) (void)hipHostFree(hbrk);
   }
   // Sizes every scratch buffer of the call and carves s5 / s3 by the one
   // layout (hgx_train_layout.h); both start the call zeroed.
@@ -747,9 +776,17 @@ struct TrainRun {
   }
   int init(int *perm) {
     HGX_TRY(buffers(perm));
-    if (p.fused)
-      HGX_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&hbrk),
-                                 sizeof(int) * p.CB * (p.overlap ? 2 : 1)));
+    if (p.fused && !merged) {
+      const size_t need = (size_t)p.CB * (p.overlap ? 2 : 1);
+      if (ctx->train_hbrk_n < need) {
+        if (ctx->train_hbrk) (void)hipHostFree(ctx->train_hbrk);
+        ctx->train_hbrk = nullptr, ctx->train_hbrk_n = 0;
+        HGX_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->train_hbrk),
+                                   sizeof(int) * need));
+        ctx->train_hbrk_n = need;
+      }
+      hbrk = ctx->train_hbrk;
+    }
     if (p.overlap && !p.ahead) {
       HGX_TRY(train_streams(ctx, ctx->tune.train_prep_cus));
       sst = ctx->tstream[0];
@@ -778,8 +815,8 @@ struct TrainRun {
   }
   // Preparation of chunk c on spr. In line it runs right before the chunk's
   // batches (the records it writes are still in the Infinity Cache when they
-  // are read). With the step it also places the chunk into set_of(c) and
-  // copies the chunk's MULTI flags to the host.
+  // are read). With the step it also places the chunk into set_of(c) and,
+  // for a form with a light kernel, copies the chunk's MULTI flags to the host.
   void prepare(int64_t c) {
     const int nbc = p.chunk_batches(c), cp = (int)(c & 1), set = set_of(c);
     hipLaunchKernelGGL(train_prep, dim3(p.CB), dim3(kTB), p.prep_smem, spr, ap[0], c * p.CB, nbc,
@@ -787,19 +824,21 @@ struct TrainRun {
     if (!p.fused) return;
     hipLaunchKernelGGL(train_place, dim3(p.CB), dim3(kTB), p.place_smem, spr, ap[set], nbc, p.CB,
                        skey[cp], sM[cp], skey[cp ^ 1], sM[cp ^ 1], c > 0 ? 1 : 0);
-    flags_err = hipMemcpyAsync(hbrk + (size_t)set * p.CB, ap[set].pbrk, sizeof(int) * nbc,
-                               hipMemcpyDeviceToHost, spr);
+    if (!merged)
+      flags_err = hipMemcpyAsync(hbrk + (size_t)set * p.CB, ap[set].pbrk, sizeof(int) * nbc,
+                                 hipMemcpyDeviceToHost, spr);
     if (p.overlap) (void)hipEventRecord(pev[c], spr);
   }
-  // Until chunk c's MULTI flags are on the host (the step; in line: one host
-  // wait per chunk of 1024 batches) and, on two streams, chunk c's steps
-  // ordered after its preparation. The two-kernel step needs neither.
+  // Until chunk c's MULTI flags are on the host (a step with a light kernel;
+  // in line: one host wait per chunk of 1024 batches) and, on two streams,
+  // chunk c's steps ordered after its preparation. The two-kernel step and,
+  // in line, a merged step need neither.
   int wait_prepared(int64_t c) {
     hipError_t e = hipSuccess;
     if (p.overlap) {
       e = hipEventSynchronize(pev[c]);
       if (e == hipSuccess && !p.ahead) (void)hipStreamWaitEvent(sst, pev[c], 0);
-    } else if (p.fused) {
+    } else if (p.fused && !merged) {
       e = flags_err != hipSuccess ? flags_err : hipStreamSynchronize(spr);
     }
     if (e == hipSuccess) return HGX_OK;
@@ -820,8 +859,7 @@ struct TrainRun {
       }
       const int64_t gbat = c * p.CB + bi;
       const int nrec = (int)std::min<int64_t>(p.batch, p.n - gbat * p.batch);
-      const int multi = hbrk[(size_t)set * p.CB + bi] && gbat > 0;
-      nmulti += multi;
+      const int multi = merged || (hbrk[(size_t)set * p.CB + bi] && gbat > 0);
       hipLaunchKernelGGL(p.kf[multi], dim3(p.NBF), dim3(p.tbf), 0, sst, ap[set], bi, (int)gbat,
                          nrec, (int)gbat);
     }
@@ -874,13 +912,15 @@ struct TrainRun {
     hipLaunchKernelGGL(loss_partial, dim3(kLossBlocks), dim3(kTB), 0, sst, ap[0].lossbuf,
                        p.nbatches * p.lstride, dpart);
     hipLaunchKernelGGL(loss_final, dim3(1), dim3(kLossBlocks), 0, sst, dpart, dloss);
-    int ovf = 0;
+    int fl[2] = {0, 0};  // ovf[0], ovf[kOvfMulti]
+    static_assert(kOvfMulti == 1, "read with the range flag");
     if (hipMemcpyAsync(&lsum, dloss, sizeof(double), hipMemcpyDeviceToHost, sst) != hipSuccess ||
-        (p.fused && hipMemcpyAsync(&ovf, ap[0].ovf, sizeof(int), hipMemcpyDeviceToHost, sst) !=
+        (p.fused && hipMemcpyAsync(fl, ap[0].ovf, sizeof(fl), hipMemcpyDeviceToHost, sst) !=
                         hipSuccess) ||
         hipStreamSynchronize(sst) != hipSuccess)
       return hgx_fail(ctx, HGX_EHIP, "epoch failed: %s", hipGetErrorString(hipGetLastError()));
-    if (ovf)
+    nmulti = fl[1];
+    if (fl[0])
       return hgx_fail(ctx, HGX_ENUMERIC,
                       "a gradient left the step's fixed-point range (|g| >= %g after "
                       "the 1/batch factor, or NaN): training diverged",

@@ -84,8 +84,9 @@ struct TrainArgs {
   // list (pfo). gacc [3][MX][dp] fixed-point sums and shadow [3][MX][2][dp]
   // base rows of deferred entries by batch parity (entries 0 / 1: row 0 of
   // the node / edge table, shadow only); r0acc the padding row's gradient
-  // sums, kR0Slots fixed-point accumulators per batch parity; ovf the
-  // fixed-point range flag.
+  // sums, kR0Slots fixed-point accumulators per batch parity; ovf[0] the
+  // fixed-point range flag, ovf[kOvfMulti] the call's count of batches
+  // train_place flagged MULTI.
   int fused, prpb, RW, MX, Mmax;
   int *pidx, *pbrk;
   unsigned *pcode, *scode;
@@ -111,6 +112,7 @@ constexpr unsigned kSlotMask = 0x3fffu;
 constexpr int kFX = 4;                      // flush slots per record group
 constexpr int kWX = kFX + 2;                // + batch words: overflow flushes,
                                             //   gacc entries to zero
+constexpr int kOvfMulti = 1;                // word of TrainArgs::ovf, see there
 constexpr int kPackB = 512;                 // max records per step batch
 constexpr int kPrepB = 1366;  // max records per prepared batch: 8192 slots / R >= 6
 constexpr int kSortP = 4096;  // prepared-batch slot count sorted by block radix sort

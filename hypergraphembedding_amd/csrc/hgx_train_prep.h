@@ -317,7 +317,13 @@ __global__ __launch_bounds__(kTB) void train_place(TrainArgs a, int nbc, int CB,
     }
   }
   __syncthreads();
-  if (threadIdx.x == 0) a.pbrk[cb] = s_brk;
+  // the flag for the forms with a light kernel; the call's count of flagged
+  // batches in ovf[kOvfMulti] (zeroed with the step buffer, read with every
+  // epoch's loss)
+  if (threadIdx.x == 0) {
+    a.pbrk[cb] = s_brk;
+    if (s_brk) atomicAdd(a.ovf + kOvfMulti, 1);
+  }
   // stable partition: records without lists first
   {
     const int per = (nb + kTB - 1) / kTB, i0 = threadIdx.x * per, i1 = min(i0 + per, nb);

@@ -1,6 +1,7 @@
 // Trainer kernels, deferred-row step: fixed point, SV<>, the row-0 helpers,
 // train_step, train_step_pair, train_step_quad and train_flush.
 #pragma once
+#include "hgx_fix.h"
 #include "hgx_train_split.h"
 
 namespace {
@@ -46,18 +47,10 @@ namespace {
 // two launches after their use (the count rides in the record words).
 // ---------------------------------------------------------------------------
 
-// fixed point of the deferred-row gradient sums: 2^44 units, |one added
-// value| < kFixLimit; at most 2^13 adds per entry and batch keep the sum
-// below 2^63. A value outside the range (a diverged run, or NaN) raises the
-// step's overflow flag and hgx_train fails with HGX_ENUMERIC.
-constexpr double kFixScale = 17592186044416.0;  // 2^44
-constexpr double kFixInv = 1.0 / 17592186044416.0;
-constexpr float kFixLimit = 32.f;
-
-// rounded to the nearest 2^-44 unit (not truncated toward zero)
-__device__ __forceinline__ unsigned long long to_fix(float v) {
-  return (unsigned long long)__double2ll_rn((double)v * kFixScale);
-}
+// fixed point of the deferred-row gradient sums: kFixScale, kFixLimit and
+// to_fix in hgx_fix.h (shared with the host check). from_fix keeps its
+// int64 -> double step: it rounds for sums above 2^53, and that rounding is
+// part of the step's bits.
 __device__ __forceinline__ float from_fix(long long v) {
   return (float)((double)v * kFixInv);
 }
@@ -115,10 +108,10 @@ struct SV<4> {
     bad |= !(fabsf(v.x) < kFixLimit) | !(fabsf(v.y) < kFixLimit) |
            !(fabsf(v.z) < kFixLimit) | !(fabsf(v.w) < kFixLimit);
     unsigned long long *d = reinterpret_cast<unsigned long long *>(e) + 4 * lane;
-    atomicAdd(d + 0, to_fix(v.x));
-    atomicAdd(d + 1, to_fix(v.y));
-    atomicAdd(d + 2, to_fix(v.z));
-    atomicAdd(d + 3, to_fix(v.w));
+    atomicAdd(d + 0, to_fix<4>(v.x));
+    atomicAdd(d + 1, to_fix<4>(v.y));
+    atomicAdd(d + 2, to_fix<4>(v.z));
+    atomicAdd(d + 3, to_fix<4>(v.w));
   }
   static __device__ __forceinline__ void zerofix(long long *e, int lane) {
     longlong2 *g = reinterpret_cast<longlong2 *>(e) + 2 * lane;
@@ -170,8 +163,8 @@ struct SV<2> {
   static __device__ __forceinline__ void addfix(long long *e, int lane, T v, int &bad) {
     bad |= !(fabsf(v.x) < kFixLimit) | !(fabsf(v.y) < kFixLimit);
     unsigned long long *d = reinterpret_cast<unsigned long long *>(e) + 2 * lane;
-    atomicAdd(d + 0, to_fix(v.x));
-    atomicAdd(d + 1, to_fix(v.y));
+    atomicAdd(d + 0, to_fix<2>(v.x));
+    atomicAdd(d + 1, to_fix<2>(v.y));
   }
   static __device__ __forceinline__ void zerofix(long long *e, int lane) {
     reinterpret_cast<longlong2 *>(e)[lane] = make_longlong2(0, 0);
@@ -345,6 +338,26 @@ __device__ __forceinline__ void row0_finish(const TrainArgs &a, int q,
 #define HGX_TRAIN_R0EARLY 1
 #endif
 
+// MULTI = true: after the first fold pass a wave that still has pending slots
+// (pm != 0, a scalar) takes a second pass and then the slot-by-slot
+// remainder; MULTI = false ends after the first pass and is correct only for
+// batches in which train_place found at most one pending entry per record,
+// so the host reads train_place's flags before it queues a chunk's launches
+// (one stream drain per chunk). A form built as MULTI = true alone (merged)
+// needs nothing from the device inside an epoch. Registers are the same
+// either way (gfx950: quad 80 / 80 VGPRs, paired 86 / 86 at float2 rows and
+// 124 / 124 at float4 rows, no scratch), the time is not (interleaved,
+// us per batch): the paired form at float4 rows (d = 256, C4
+// slice, where most batches are MULTI) 8.361 -> 8.319 merged; the quad form
+// (d = 128, C3) 5.607 -> 5.804 at 2 records per workgroup and 5.314 -> 5.545
+// at 1, of which 0.09 is the kernel and the rest the launch queue kept full.
+// HGX_TRAIN_ONEKERNEL: 1 (default) merges the paired form at float4 rows; 0 /
+// 2 (A/B builds): no form / the paired and the quad form at every width. The
+// one-wave forms keep the two instantiations.
+#ifndef HGX_TRAIN_ONEKERNEL
+#define HGX_TRAIN_ONEKERNEL 1
+#endif
+
 // The paired-wave form of the step (PAIR, 64 lanes per record, 512 threads):
 // one record on two waves of the workgroup, wave 2g the node half of record
 // g and wave 2g + 1 its edge half, still 4 records per workgroup and the same
@@ -505,7 +518,9 @@ __device__ __forceinline__ void train_step_pair(const TrainArgs &a, int cb, int 
       pm &= ~wm;
     };
     fold_pass();
-    if (MULTI) {
+    // (wave-uniform: pm sits in scalar registers; a light batch pays one
+    // scalar compare for the merged kernel)
+    if (MULTI && pm != 0) {
       fold_pass();
       if (pm != 0) {
 #pragma unroll
@@ -689,11 +704,13 @@ __device__ __forceinline__ void train_step_pair(const TrainArgs &a, int cb, int 
 // the paired form's whole 7-slot program (role kQFull) and its list wave only
 // reaches the barriers (kQIdle); a wave-uniform test on the codes both waves
 // hold. Flush slot 0 rides on the list wave of its table, flush slots 1..
-// on waves 1..3 of the record. Same placed buffers, placed for RPB = 2: 128
-// workgroups of 512 threads, half the paired form's gathers, stores and
-// atomics per CU. Float2 rows (padded d = 128) only: the 4-record,
-// 1024-thread geometry measured slower than the paired form at both row
-// widths, and at float4 rows the padding row's gradient is a
+// on waves 1..3 of the record. Same placed buffers, placed for RPB records
+// per workgroup. RPB = 1 (the default at d = 128): 256 workgroups of 256
+// threads, a batch of 256 on every CU, 4 waves at each barrier; RPB = 2: 128
+// workgroups of 512 threads (interleaved on C3 HOBE records: 5.607 us per
+// batch at 2, 5.314 at 1). Float2 rows (padded d = 128) only: the
+// 4-record, 1024-thread geometry measured slower than the paired form at
+// both row widths, and at float4 rows the padding row's gradient is a
 // float sum over the workgroup's records, bit-identical to the other forms
 // only over their four.
 enum { kQFull = 0, kQHead = 1, kQList = 2, kQIdle = 3 };
@@ -873,7 +890,7 @@ __device__ __forceinline__ void train_step_quad(const TrainArgs &a, int cb, int 
         pm &= ~wm;
       };
       fold_pass();
-      if (MULTI) {
+      if (MULTI && pm != 0) {  // (wave-uniform, as in the paired form)
         fold_pass();
         if (pm != 0) {
 #pragma unroll

@@ -84,6 +84,8 @@ int hgx_mem_info(hgx_ctx *ctx, int64_t *free_bytes, int64_t *total_bytes);
  *                      per workgroup; overrides train_tb), 3 one record on
  *                      four waves (each table half on a head and a list
  *                      wave), 2 records per 512-thread workgroup (padded
+ *                      d = 128; at 256 the same as 1), 4 the same four
+ *                      waves, 1 record per 256-thread workgroup (padded
  *                      d = 128; at 256 the same as 1), 0 one wave per
  *                      record, -1 per geometry where train_tb is 0
  *                      (default); bit-identical

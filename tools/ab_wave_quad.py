@@ -1,6 +1,7 @@
 """Interleaved A/B of the trainer step's quad form (tuning `train_wave_pair`:
 1 one record on two waves, 3 on four waves with 2 records per 512-thread
-workgroup; arms the library does not build, such as the 4-record geometry 2
+workgroup, 4 on four waves with 1 record per 256-thread workgroup; arms the
+library does not build, such as the 4-record geometry 2
 of the first measurements, are skipped) in one process: epochs alternate between
 the settings on the same records and initial model, per-batch device time
 (hgx_train_last_stats, HIP events) per setting. Diagnostic only.
@@ -27,7 +28,7 @@ rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 6
 frac = float(sys.argv[3]) if len(sys.argv) > 3 else 0.02
 ctx = _hgx.Context(0)
 ARMS = [1]
-for arm in (2, 3):
+for arm in (2, 3, 4):
   try:
     ctx.set_tuning("train_wave_pair", arm)
     ARMS.append(arm)
