@@ -1599,6 +1599,7 @@ extern "C" int hgx_alg_shard_begin(hgx_ctx *ctx, int32_t row0, int32_t row1,
   ctx->row1 = row1;
   ctx->ext_wire = nullptr;
   ctx->n_wire = 0;
+  ctx->wire_map = false;
   ctx->ext_partial = (float *)d_partial;
   ctx->ext_mm = (int *)d_mm;
   ctx->ext_iters = iters;
@@ -1723,6 +1724,7 @@ extern "C" int hgx_alg_shard_wire(hgx_ctx *ctx, void *d_wire, int64_t n_shared,
                          hipMemcpyHostToDevice));
   ctx->ext_wire = (float *)d_wire;
   ctx->n_wire = n_shared;
+  ctx->wire_map = true;
   return HGX_OK;
 }
 
@@ -1734,7 +1736,10 @@ extern "C" int hgx_alg_shard_edge_final(hgx_ctx *ctx, int it) {
   const int *prev = it ? ctx->ext_mm + slot * (it - 1) : nullptr;
   int *cur = ctx->ext_mm + slot * it;
   float *yc = ctx->Y[ctx->ycur].as<float>(), *yn = ctx->Y[ctx->ycur ^ 1].as<float>();
-  if (ctx->ext_wire)
+  // with a slot map and no shared edge the wire is null and never read
+  // (no slot is >= 0); the dense kernel would finish the other ranks'
+  // private edges from this rank's empty partial: 0 / 0 in the min/max words
+  if (ctx->wire_map)
     hipLaunchKernelGGL(algdist_edge_final_wire,
                        dim3(grid_for((int64_t)ctx->E * ctx->ks, 256)), dim3(256),
                        0, ctx->stream, ctx->E, ctx->ks, ctx->k,
@@ -1762,5 +1767,6 @@ extern "C" int hgx_alg_shard_end(hgx_ctx *ctx) {
   ctx->ext_partial = nullptr;
   ctx->ext_wire = nullptr;
   ctx->n_wire = 0;
+  ctx->wire_map = false;
   return HGX_OK;
 }

@@ -160,6 +160,9 @@ struct hgx_ctx {
   float *ext_wire = nullptr;
   int64_t n_wire = 0;
   DevBuf wire_slot;
+  // a slot map is installed; it may name no shared edge (n_wire == 0, null
+  // wire), and edge_final still has to skip the other ranks' private edges
+  bool wire_map = false;
   int *ext_mm = nullptr;         // iters x 2 x ks
   int ext_iters = 0;
   double alg_ms = 0, alg_bytes = 0;
