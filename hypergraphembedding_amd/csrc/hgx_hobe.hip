@@ -9,12 +9,16 @@
 // :607-616 is disabled).
 // hg2v_weighting.py:195-198 (UniformWeight), 137-167 (WeightByNeighborhood).
 //
-// Bit-exactness with numpy: np.linalg.norm of a float32 vector of length
-// k < 32 runs OpenBLAS sdot's tail loop -- float products accumulated in a
-// DOUBLE, cast to float, then a float sqrt. The weight kernel does the same
-// with explicitly rounded products (no contraction) and a correctly rounded
-// sqrt and divide. w is symmetric bit for bit (the difference only changes
-// sign), so one weight per incidence serves both orientations: `hw_n` in
+// Bit-exactness with numpy at every k: np.linalg.norm of a float32 vector of
+// length k < 32 runs OpenBLAS sdot's tail loop -- float products accumulated
+// in a DOUBLE, cast to float, then a float sqrt. The weight kernel does the
+// same with explicitly rounded products (no contraction) and a correctly
+// rounded sqrt and divide. From k = 32 on numpy runs sdot's blocked kernel,
+// which norm32 (hgx_norm32.h) restates; the weight kernel's second
+// instantiation, chosen on the host, takes its norm from there (pinned to
+// numpy's own output at k = 40 by tests/golden/weights_dist.npz). w is
+// symmetric bit for bit (the difference only changes sign, and squares in
+// the same order), so one weight per incidence serves both orientations: `hw_n` in
 // A's CSR order (node v, edge e), `hw_e` in A^T's (edge e, node u), and
 // `hw_self[e]` = max_u w(e, u). Everything downstream is max / min of these
 // values, so any evaluation order gives the reference's result exactly.
@@ -38,19 +42,28 @@
 #include <vector>
 
 #include "hgx_internal.h"
+#include "hgx_norm32.h"
 
 namespace {
 
-// a, b: coordinate rows in the [w, c_0..c_{k-1}, pad] layout.
+// a, b: coordinate rows in the [w, c_0..c_{k-1}, pad] layout. kBlocked:
+// k >= 32, numpy's blocked norm (the k < 32 instantiation is the tail loop
+// alone, and keeps its registers).
+template <bool kBlocked>
 __device__ __forceinline__ float dist_weight(const float *__restrict__ a,
                                              const float *__restrict__ b,
                                              int k) {
-  double acc = 0.0;
-  for (int d = 1; d <= k; d++) {
-    const float df = __fsub_rn(a[d], b[d]);
-    acc += (double)__fmul_rn(df, df);
+  float nrm;
+  if constexpr (kBlocked) {
+    nrm = hgx::norm32(a + 1, b + 1, k);
+  } else {
+    double acc = 0.0;
+    for (int d = 1; d <= k; d++) {
+      const float df = __fsub_rn(a[d], b[d]);
+      acc += (double)__fmul_rn(df, df);
+    }
+    nrm = (float)sqrt((double)(float)acc);
   }
-  const float nrm = (float)sqrt((double)(float)acc);
   const float md = (float)sqrt((double)k);
   return __fdiv_rn(__fsub_rn(md, nrm), md);
 }
@@ -74,14 +87,12 @@ struct HobeW {
   const float *self;  // per edge: max_u w(e, u)
 };
 
-// w for every incidence, in the order of the given CSR (rows of `rowtab`,
-// columns of `coltab`).
+// Uniform (which 0) or neighbourhood (which 1) weight of every incidence, in
+// the order of the given CSR. The distance weights (which 2) are
+// hobe_weight_kernel's.
 __global__ void incidence_weight_kernel(int which, double alpha, int R,
                                         const int *__restrict__ rp,
                                         const int *__restrict__ col,
-                                        const float *__restrict__ rowtab,
-                                        const float *__restrict__ coltab,
-                                        int KS, int k,
                                         const int *__restrict__ rp_other,
                                         int other_min, int other_max,
                                         float *__restrict__ out) {
@@ -92,7 +103,7 @@ __global__ void incidence_weight_kernel(int which, double alpha, int R,
       float w;
       if (which == 0) {
         w = 1.0f;
-      } else if (which == 1) {
+      } else {
         // weight of incidence (r, c) = neighbourhood factor of the COLUMN
         // entity: alpha + (1-alpha) * (1 - zero_one(|c|)), double math,
         // rounded to float once (DictToSparseRow stores float32).
@@ -101,8 +112,6 @@ __global__ void incidence_weight_kernel(int which, double alpha, int R,
                        ? 1.0
                        : (double)(sz - other_min) / (double)(other_max - other_min);
         w = (float)(alpha + (1.0 - alpha) * (1.0 - z));
-      } else {
-        w = dist_weight(rowtab + (size_t)r * KS, coltab + (size_t)c * KS, k);
       }
       out[t] = w;
     }
@@ -114,6 +123,7 @@ __global__ void incidence_weight_kernel(int which, double alpha, int R,
 // edge-major pass also each edge's max weight (order-free atomicMax on the
 // bits of non-negative floats; negative weights never win a max that
 // starts at 0).
+template <bool kBlocked>
 __global__ void hobe_weight_kernel(int64_t nnz, int R, const int *__restrict__ rp,
                                    const int *__restrict__ col,
                                    const float *__restrict__ rowtab,
@@ -135,7 +145,8 @@ __global__ void hobe_weight_kernel(int64_t nnz, int R, const int *__restrict__ r
         if (rp[mid] <= t) lo = mid;
         else hi = mid - 1;
       }
-      w = dist_weight(rowtab + (size_t)lo * KS, coltab + (size_t)col[t] * KS, k);
+      w = dist_weight<kBlocked>(rowtab + (size_t)lo * KS,
+                                coltab + (size_t)col[t] * KS, k);
       out[t] = w;
     }
     if (!rowmax) continue;
@@ -492,12 +503,14 @@ int hgx_hobe_prepare(hgx_ctx *ctx) {
   if (nnz == 0) return HGX_OK;
   const float *X = ctx->X[ctx->xcur].as<float>();
   const float *Y = ctx->Y[ctx->ycur].as<float>();
-  hipLaunchKernelGGL(hobe_weight_kernel, dim3(grid_for(nnz, 256, 65536)),
+  // numpy's norm switches kernels at k = 32 (see the header)
+  const auto kern = ctx->k >= 32 ? hobe_weight_kernel<true> : hobe_weight_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(grid_for(nnz, 256, 65536)),
                      dim3(256), 0, ctx->stream, nnz, ctx->N, ctx->rp_n.as<int>(),
                      ctx->col_n.as<int>(), X, Y, ctx->ks, ctx->k,
                      ctx->hw_n.as<float>(), (unsigned *)nullptr);
   HGX_LAUNCH_CHECK(ctx);
-  hipLaunchKernelGGL(hobe_weight_kernel, dim3(grid_for(nnz, 256, 65536)),
+  hipLaunchKernelGGL(kern, dim3(grid_for(nnz, 256, 65536)),
                      dim3(256), 0, ctx->stream, nnz, ctx->E, ctx->rp_e.as<int>(),
                      ctx->col_e.as<int>(), Y, X, ctx->ks, ctx->k,
                      ctx->hw_e.as<float>(), ctx->hw_self.as<unsigned>());
@@ -585,13 +598,13 @@ extern "C" int hgx_incidence_weights(hgx_ctx *ctx, int which, double alpha,
       hipLaunchKernelGGL(incidence_weight_kernel, dim3(grid_for(ctx->N, 256)),
                          dim3(256), 0, ctx->stream, which, alpha,
                          ctx->N, ctx->rp_n.as<int>(), ctx->col_n.as<int>(),
-                         nullptr, nullptr, 0, 0, ctx->rp_e.as<int>(), smin, smax,
+                         ctx->rp_e.as<int>(), smin, smax,
                          ctx->s4.as<float>());
     else
       hipLaunchKernelGGL(incidence_weight_kernel, dim3(grid_for(ctx->E, 256)),
                          dim3(256), 0, ctx->stream, which, alpha,
                          ctx->E, ctx->rp_e.as<int>(), ctx->col_e.as<int>(),
-                         nullptr, nullptr, 0, 0, ctx->rp_n.as<int>(), dmin, dmax,
+                         ctx->rp_n.as<int>(), dmin, dmax,
                          ctx->s4.as<float>());
     HGX_LAUNCH_CHECK(ctx);
     HGX_HIP(ctx, hipMemcpyAsync(host, ctx->s4.p, sizeof(float) * ctx->nnz,

@@ -207,7 +207,8 @@ int hgx_alg_shard_edge_partial_range(hgx_ctx *ctx, int it, int r);
  * (:588-629) on the device-resident alg coords (after hgx_alg_run or
  * hgx_alg_set; values are used exactly as given, i.e. already rescaled).
  * kind: 0 node-node, 1 edge-edge, 2 node-edge. Bit-exact with numpy's
- * float32 norm (double-accumulated float products, k < 32). */
+ * float32 norm at every k (double-accumulated float products below k = 32,
+ * the blocked sdot kernel of csrc/hgx_norm32.h from there on). */
 int hgx_hobe_probs(hgx_ctx *ctx, int kind, int64_t n, const int32_t *a,
                    const int32_t *b, float *out);
 

@@ -458,24 +458,31 @@ int64_t hgref_fobe_sample(hgref_rng *s, int64_t N, int64_t E,
 /* HOBE probabilities.                                                        */
 /* _same_type_dist_calc (hg2v_sample.py:527-543): for pair (i,j) over the    */
 /* shared targets t: w = (sqrt(k) - ||a_i - a_t||_2)/sqrt(k) in float32,      */
-/* prob = max_t min(w_it, w_jt), 0 when nothing is shared. numpy's norm of a */
-/* float32 vector with k<32 is OpenBLAS sdot's tail loop: float products     */
-/* accumulated in a double, then cast to float; sqrt in float32.             */
+/* prob = max_t min(w_it, w_jt), 0 when nothing is shared. The norm is       */
+/* numpy's at every k (hgref_norm32 below): with k<32 OpenBLAS sdot's tail   */
+/* loop alone (float products accumulated in a double, then cast to float;   */
+/* sqrt in float32), from k=32 on its blocked kernel first.                  */
 /* ------------------------------------------------------------------------- */
+float hgref_norm32(const float *a, const float *b, int k, int norm);
+
 static float dist_weight(const float *a, const float *b, int k) {
-  double acc = 0.0;
-  for (int d = 0; d < k; d++) {
-    float df = a[d] - b[d];
-    float pr = df * df;
-    acc += (double)pr;
-  }
-  float nrm = sqrtf((float)acc);
+  float nrm = hgref_norm32(a, b, k, 0);
   float md = (float)sqrt((double)k);
   return (md - nrm) / md;
 }
 
 float hgref_dist_weight(const float *a, const float *b, int k) {
   return dist_weight(a, b, k);
+}
+
+/* w of every incidence in A's CSR order (the device's per-incidence HOBE
+ * weights; the edge-major ones are a permutation of these) */
+void hgref_hobe_weights(int64_t N, const int32_t *rp_n, const int32_t *col_n,
+                        const float *alg_node, const float *alg_edge, int k,
+                        float *out) {
+  for (int64_t v = 0; v < N; v++)
+    for (int32_t t = rp_n[v]; t < rp_n[v + 1]; t++)
+      out[t] = dist_weight(alg_node + v * k, alg_edge + (int64_t)col_n[t] * k, k);
 }
 
 /* first position in [lo, hi) of col with col[pos] >= v (galloping then

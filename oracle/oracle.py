@@ -66,6 +66,8 @@ def lib():
                                    _i32p, _i32p, _f32p, _f32p, _int, _f32p]
     L.hgref_dist_weight.restype = ctypes.c_float
     L.hgref_dist_weight.argtypes = [_f32p, _f32p, _int]
+    L.hgref_hobe_weights.argtypes = [_i64, _i32p, _i32p, _f32p, _f32p, _int,
+                                     _f32p]
     L.hgref_train.restype = _int
     L.hgref_train.argtypes = [_i64, _int, _i32p, _f32p, _int, _i64, _i64,
                               _f32p, _f32p, _f32p, _f32p, _int, _int, _int,
@@ -247,6 +249,16 @@ def hobe_probs(kind, a, b, inc, alg_node, alg_edge):
   out = np.empty(a.size, np.float32)
   lib().hgref_hobe_probs(kind, a.size, a, b, inc.rp_n, inc.col_n, inc.rp_e,
                          inc.col_e, alg_node, alg_edge, alg_node.shape[1], out)
+  return out
+
+
+def hobe_weights(inc, alg_node, alg_edge):
+  """The HOBE weight of every incidence, node-major (A's CSR order)."""
+  alg_node = np.ascontiguousarray(alg_node, np.float32)
+  alg_edge = np.ascontiguousarray(alg_edge, np.float32)
+  out = np.empty(inc.nnz, np.float32)
+  lib().hgref_hobe_weights(inc.N, inc.rp_n, inc.col_n, alg_node, alg_edge,
+                           alg_node.shape[1], out)
   return out
 
 
