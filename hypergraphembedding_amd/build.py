@@ -18,6 +18,15 @@ INCLUDE = os.path.join(ROOT, "include")
 ARCH = os.environ.get("HGX_OFFLOAD_ARCH", "gfx950")
 
 
+# Per-source flags. The trainer's step kernels address their record words
+# from the scalar arguments ahead of the by-value TrainArgs (HGX_STEP_PARAMS
+# in csrc/hgx_train_step.h); preloading delivers those in SGPRs at wave start
+# instead of behind a scalar load.
+EXTRA_FLAGS = {
+    "hgx_train.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=12"],
+}
+
+
 def _sources():
   return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
 
@@ -51,7 +60,8 @@ def build(force=False, verbose=False):
         for p in [src] + glob.glob(os.path.join(CSRC, "*.h")) +
         [os.path.join(INCLUDE, "hgx.h")]):
       continue
-    cmd = [hipcc] + flags + ["-c", src, "-o", obj]
+    cmd = ([hipcc] + flags + EXTRA_FLAGS.get(os.path.basename(src), []) +
+           ["-c", src, "-o", obj])
     if verbose:
       print(" ".join(cmd), file=sys.stderr)
     procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE,

@@ -94,7 +94,13 @@ KFn fwd_for(int K, int loss, int act, int tb1) {
   return train_fwd_bwd<L, VPL, 16, false, 0, kTB>;
 }
 
+// (the step's parameter list: HGX_STEP_PARAMS in hgx_train_step.h)
+#if HGX_TRAIN_PRELOAD
+using KStepFn = void (*)(const int *, const unsigned *, const float *, int, int, int, float, int,
+                         int, TrainArgs);
+#else
 using KStepFn = void (*)(TrainArgs, int, int, int, int);
+#endif
 using KFlushFn = void (*)(TrainArgs, const int *, const int *, const int *, int, int);
 
 // deferred-row step: d in (64, 256], K = 5 with the FOBE (sigmoid/KLD) or
@@ -860,8 +866,18 @@ struct TrainRun {
       const int64_t gbat = c * p.CB + bi;
       const int nrec = (int)std::min<int64_t>(p.batch, p.n - gbat * p.batch);
       const int multi = merged || (hbrk[(size_t)set * p.CB + bi] && gbat > 0);
+#if HGX_TRAIN_PRELOAD
+      // the batch's record words in the placed set, and 1 / records (the
+      // division the step did on every wave)
+      const TrainArgs &as = ap[set];
+      const size_t g0 = (size_t)bi * p.NBF * p.prpb;
+      hipLaunchKernelGGL(p.kf[multi], dim3(p.NBF), dim3(p.tbf), 0, sst, as.pidx + g0 * p.RW,
+                         as.pcode + g0 * p.RW, as.ptgt + g0 * 3, p.RW, nrec, (int)gbat,
+                         1.0f / (float)nrec, (int)gbat, bi, as);
+#else
       hipLaunchKernelGGL(p.kf[multi], dim3(p.NBF), dim3(p.tbf), 0, sst, ap[set], bi, (int)gbat,
                          nrec, (int)gbat);
+#endif
     }
     (p.fused ? nfused : nsplit) += nbc;
   }

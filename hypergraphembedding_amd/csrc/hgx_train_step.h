@@ -1,6 +1,7 @@
 // Trainer kernels, deferred-row step: fixed point, SV<>, the row-0 helpers,
 // train_step, train_step_pair, train_step_quad and train_flush.
 #pragma once
+#include "hgx_divk.h"
 #include "hgx_fix.h"
 #include "hgx_train_split.h"
 
@@ -47,12 +48,65 @@ namespace {
 // two launches after their use (the count rides in the record words).
 // ---------------------------------------------------------------------------
 
+// Kernel arguments of the step. Round trip 1 (the record words) is addressed
+// from scalars alone, placed ahead of the by-value TrainArgs so that the
+// translation unit's kernel-argument preloading (build.py) delivers them in
+// SGPRs at wave start: the chunk-local batch's bases into the placed buffers
+// (pidx / pcode / ptgt + cb NBF RPB words, computed by the driver), RW, the
+// batch's record count, q, and 1 / records (IEEE single division is
+// correctly rounded on the host as on the device: the same bits). A by-value
+// struct ends preloading, so it comes last. HGX_TRAIN_PRELOAD=0 (A/B
+// builds): TrainArgs first, the bases formed in the kernel from a.pidx and
+// cb, two dependent scalar round trips ahead of the record-word loads.
+// HGX_TRAIN_HOSTINVB=0 (A/B builds): 1 / records divided on every wave.
+#ifndef HGX_TRAIN_PRELOAD
+#define HGX_TRAIN_PRELOAD 1
+#endif
+#ifndef HGX_TRAIN_HOSTINVB
+#define HGX_TRAIN_HOSTINVB HGX_TRAIN_PRELOAD
+#endif
+struct StepWords {
+  const int *pidx;  // this batch's record words, workgroup 0's first group
+  const unsigned *pcode;
+  const float *ptgt;
+  int RW;
+  float inv_b;
+};
+#if HGX_TRAIN_PRELOAD
+#define HGX_STEP_PARAMS                                                              \
+  const int *w_pidx, const unsigned *w_pcode, const float *w_ptgt, int w_rw, int nb, \
+      int q, float w_inv_b, int gb, int cb, TrainArgs a
+#define HGX_STEP_WORDS(RPB)                                \
+  const StepWords w = {w_pidx, w_pcode, w_ptgt, w_rw,      \
+                       HGX_TRAIN_HOSTINVB ? w_inv_b : 1.0f / (float)nb}
+#else
+#define HGX_STEP_PARAMS TrainArgs a, int cb, int gb, int nb, int q
+#define HGX_STEP_WORDS(RPB)                                                       \
+  const size_t w_g0 = (size_t)cb * gridDim.x * (RPB);                             \
+  const StepWords w = {a.pidx + w_g0 * a.RW, a.pcode + w_g0 * a.RW, a.ptgt + w_g0 * 3, \
+                       a.RW, 1.0f / (float)nb}
+#endif
+
 // fixed point of the deferred-row gradient sums: kFixScale, kFixLimit and
 // to_fix in hgx_fix.h (shared with the host check). from_fix keeps its
 // int64 -> double step: it rounds for sums above 2^53, and that rounding is
 // part of the step's bits.
 __device__ __forceinline__ float from_fix(long long v) {
   return (float)((double)v * kFixInv);
+}
+// The head math's divisions by the neighbour count (the two means and the
+// mean's gradient, on every wave of a record between the exchange barrier
+// and the first store): div_const of hgx_divk.h for the K it is proven
+// bit-equal to the division for, the division otherwise. Every form of the
+// step goes through here (train_flush divides nothing by K).
+// HGX_TRAIN_DIVK=0 (A/B builds): the IEEE division.
+#ifndef HGX_TRAIN_DIVK
+#define HGX_TRAIN_DIVK 1
+#endif
+template <int K>
+__device__ __forceinline__ float div_k(float x) {
+  if constexpr (HGX_TRAIN_DIVK && K == 5) return div_const<K>(x);
+  else return x / (float)K;
 }
 // The step's scalar head math (contraction off, see mul_nc)
 __device__ __forceinline__ float act_d_nc(int act, float z, float y) {
@@ -373,8 +427,8 @@ __device__ __forceinline__ void row0_finish(const TrainArgs &a, int q,
 // rows, pending slots and the padding-row sums are all per table, so no other
 // state crosses the pair. Own slots are j = 0 (H), 1 (O), 2 + k (Tk).
 template <int VW, int K, int MODE, bool MULTI>
-__device__ __forceinline__ void train_step_pair(const TrainArgs &a, int cb, int gb, int nb,
-                                                int q) {
+__device__ __forceinline__ void train_step_pair(const TrainArgs &a, const StepWords &w,
+                                                int cb, int gb, int nb, int q) {
   constexpr int L = 64, RPB = 4, NW = 2 * RPB, TB = NW * L, R = 4 + 2 * K, J = 2 + K;
   constexpr int NZ = 1 + K;  // head dots of one half
   using S = SV<VW>;
@@ -392,15 +446,15 @@ __device__ __forceinline__ void train_step_pair(const TrainArgs &a, int cb, int 
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / L), lane = threadIdx.x % L;
   const int grp = wave >> 1, half = wave & 1;  // half 1: the edge wave
   const bool edge = half;
-  const int NBF = gridDim.x, RW = a.RW;
+  const int NBF = gridDim.x, RW = w.RW;
   const int par = q % 3, ppar = (q + 2) % 3, zpar = (q + 1) % 3;
   // round trip 1: as the unpaired form, both waves of a pair loading their
   // record's words; the padding-row loads by the column owners only (waves
   // 0 and 1: the node and the edge table's row 0)
-  const size_t gi = ((size_t)cb * NBF + blockIdx.x) * RPB + grp;
-  const int *ri = a.pidx + gi * RW;
-  const unsigned *rc = a.pcode + gi * RW;
-  const float *yt = a.ptgt + gi * 3;
+  const unsigned gi = blockIdx.x * RPB + grp;  // (32-bit: at most kPackB groups of RW words)
+  const int *ri = w.pidx + gi * RW;
+  const unsigned *rc = w.pcode + gi * RW;
+  const float *yt = w.ptgt + gi * 3;
   const int sl = lane < RW ? lane : 0;
   const int rv = ri[sl];
   const int cv = (int)rc[sl];
@@ -557,7 +611,7 @@ __device__ __forceinline__ void train_step_pair(const TrainArgs &a, int cb, int 
         sk[k] = act_f(act, zk[k]);
         PQ += sk[k];
       }
-      PQ = PQ / (float)K;
+      PQ = div_k<K>(PQ);
       if (lane == 0) {
         s_x[grp][half] = PQ;
         if (edge) s_x[grp][2] = yh;
@@ -567,7 +621,7 @@ __device__ __forceinline__ void train_step_pair(const TrainArgs &a, int cb, int 
     V zT = S::zero();  // this table's padding-row gradient sum
     float lrec = 0.f;
     if (has) {
-      const float inv_b = 1.0f / (float)nb;
+      const float inv_b = w.inv_b;
       const V &H = Pv[0], &O = Pv[1];
       const float P = s_x[grp][0], Q = s_x[grp][1];
       const float y3 = mul_nc(P, Q);
@@ -586,7 +640,7 @@ __device__ __forceinline__ void train_step_pair(const TrainArgs &a, int cb, int 
       g3 *= inv_b;
       const float dz = gh * act_d_nc(act, zh, yh);
       // dP = g3 Q / K on the node wave, dQ = g3 P / K on the edge wave
-      const float dk = g3 * (edge ? P : Q) / (float)K;
+      const float dk = div_k<K>(g3 * (edge ? P : Q));
       auto emit = [&](int j, V g) {
         const unsigned cd = code[j];
         if (row[j] == 0) {
@@ -729,8 +783,8 @@ struct QC {
   static constexpr int value = V;
 };
 template <int VW, int K, int MODE, bool MULTI, int RPB>
-__device__ __forceinline__ void train_step_quad(const TrainArgs &a, int cb, int gb, int nb,
-                                                int q) {
+__device__ __forceinline__ void train_step_quad(const TrainArgs &a, const StepWords &w,
+                                                int cb, int gb, int nb, int q) {
   constexpr int L = 64, NW = 4 * RPB, TB = NW * L, R = 4 + 2 * K, J = 2 + K;
   constexpr int KH = 1, JH = 2 + KH, KL = K - KH;  // list rows of the head / list wave
   constexpr int NZ = 1 + K;                        // head dots of one half
@@ -751,14 +805,14 @@ __device__ __forceinline__ void train_step_quad(const TrainArgs &a, int cb, int 
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / L), lane = threadIdx.x % L;
   const int grp = wave >> 2, half = (wave >> 1) & 1, sub = wave & 1;  // sub 1: the list wave
   const bool edge = half;
-  const int NBF = gridDim.x, RW = a.RW;
+  const int NBF = gridDim.x, RW = w.RW;
   const int par = q % 3, ppar = (q + 2) % 3, zpar = (q + 1) % 3;
   // round trip 1: as the paired form, all four waves loading their record's
   // words; the padding-row loads by waves 0 and 1 (node / edge table's row 0)
-  const size_t gi = ((size_t)cb * NBF + blockIdx.x) * RPB + grp;
-  const int *ri = a.pidx + gi * RW;
-  const unsigned *rc = a.pcode + gi * RW;
-  const float *yt = a.ptgt + gi * 3;
+  const unsigned gi = blockIdx.x * RPB + grp;  // (32-bit: at most kPackB groups of RW words)
+  const int *ri = w.pidx + gi * RW;
+  const unsigned *rc = w.pcode + gi * RW;
+  const float *yt = w.ptgt + gi * 3;
   const int sl = lane < RW ? lane : 0;
   const int rv = ri[sl];
   const int cv = (int)rc[sl];
@@ -932,7 +986,7 @@ __device__ __forceinline__ void train_step_quad(const TrainArgs &a, int cb, int 
       using QR = QRole<decltype(rl)::value, J, JH>;
       constexpr int ROLE = decltype(rl)::value;
       // the paired form's head math, on every wave of the record
-      const float inv_b = 1.0f / (float)nb;
+      const float inv_b = w.inv_b;
       const float *zo = s_zx[grp][half], *zp = s_zx[grp][half ^ 1];
       const float zh = zo[0], yh = act_f(act, zh);
       float zk[K], sk[K], PQo = 0.f, PQp = 0.f;
@@ -942,10 +996,10 @@ __device__ __forceinline__ void train_step_quad(const TrainArgs &a, int cb, int 
         sk[k] = act_f(act, zk[k]);
         PQo += sk[k];
       }
-      PQo = PQo / (float)K;
+      PQo = div_k<K>(PQo);
 #pragma unroll
       for (int k = 0; k < K; k++) PQp += act_f(act, zp[1 + k]);
-      PQp = PQp / (float)K;
+      PQp = div_k<K>(PQp);
       const float P = edge ? PQp : PQo, Q = edge ? PQo : PQp;
       const float y3 = mul_nc(P, Q);
       float lh, l3, gh, g3, lrec = 0.f;
@@ -963,7 +1017,7 @@ __device__ __forceinline__ void train_step_quad(const TrainArgs &a, int cb, int 
       g3 *= inv_b;
       const float dz = gh * act_d_nc(act, zh, yh);
       // dP = g3 Q / K on the node waves, dQ = g3 P / K on the edge waves
-      const float dk = g3 * (edge ? P : Q) / (float)K;
+      const float dk = div_k<K>(g3 * (edge ? P : Q));
       const V &H = Pv[0], &O = Pv[1];
       auto emit = [&](int j, V g) __attribute__((always_inline)) {
         const unsigned cd = code[j];
@@ -1051,17 +1105,18 @@ __device__ __forceinline__ void train_step_quad(const TrainArgs &a, int cb, int 
 }
 
 template <int VW, int KMAX, int MODE, bool MULTI, int RPB>
-__global__ __launch_bounds__(256 * RPB) void train_step_q(TrainArgs a, int cb, int gb, int nb,
-                                                          int q) {
-  train_step_quad<VW, KMAX, MODE, MULTI, RPB>(a, cb, gb, nb, q);
+__global__ __launch_bounds__(256 * RPB) void train_step_q(HGX_STEP_PARAMS) {
+  HGX_STEP_WORDS(RPB);
+  train_step_quad<VW, KMAX, MODE, MULTI, RPB>(a, w, cb, gb, nb, q);
 }
 
 // PAIR: the paired-wave form above (L = 64, TB = 512, 4 records per workgroup)
 template <int L, int VW, int KMAX, int MODE, int TB, bool MULTI, bool PAIR = false>
-__global__ __launch_bounds__(TB) void train_step(TrainArgs a, int cb, int gb, int nb, int q) {
+__global__ __launch_bounds__(TB) void train_step(HGX_STEP_PARAMS) {
+  HGX_STEP_WORDS(PAIR ? 4 : TB / L);
   if constexpr (PAIR) {
     static_assert(!PAIR || (L == 64 && TB == 512), "paired geometry");
-    train_step_pair<VW, KMAX, MODE, MULTI>(a, cb, gb, nb, q);
+    train_step_pair<VW, KMAX, MODE, MULTI>(a, w, cb, gb, nb, q);
     return;
   }
   constexpr int RPB = TB / L, R = 4 + 2 * KMAX, K = KMAX, NC = 2 * L;
@@ -1079,15 +1134,15 @@ __global__ __launch_bounds__(TB) void train_step(TrainArgs a, int cb, int gb, in
   unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (g_trace) ts[0] = __builtin_amdgcn_s_memrealtime();
   const int grp = threadIdx.x / L, lane = threadIdx.x % L;
-  const int NBF = gridDim.x, RW = a.RW;
+  const int NBF = gridDim.x, RW = w.RW;
   const int par = q % 3, ppar = (q + 2) % 3, zpar = (q + 1) % 3;
   // round trip 1 (kernel arguments only): record ids and slot codes (one
   // load per lane, readlane broadcast), flush slots, the batch words,
   // targets, the row-0 base and the previous batch's row-0 partials
-  const size_t gi = ((size_t)cb * NBF + blockIdx.x) * RPB + grp;
-  const int *ri = a.pidx + gi * RW;
-  const unsigned *rc = a.pcode + gi * RW;
-  const float *yt = a.ptgt + gi * 3;
+  const unsigned gi = blockIdx.x * RPB + grp;  // (32-bit: at most kPackB groups of RW words)
+  const int *ri = w.pidx + gi * RW;
+  const unsigned *rc = w.pcode + gi * RW;
+  const float *yt = w.ptgt + gi * 3;
   int row[R], frow[kFX];
   unsigned code[R], fcode[kFX];
   int nfo, zc;  // batch words: overflow flushes, gacc entries to zero
@@ -1280,7 +1335,7 @@ __global__ __launch_bounds__(TB) void train_step(TrainArgs a, int cb, int gb, in
 #pragma unroll
       for (int s = 0; s < R; s++)
         if (row[s] == 0) Pv[s] = s_r0[slot_is_edge(s, K) ? 1 : 0][lane];
-      const float inv_b = 1.0f / (float)nb;
+      const float inv_b = w.inv_b;
       const V &Nl = Pv[0], &El = Pv[1], &Nr = Pv[2], &Er = Pv[3];
       float z1, z2, za[K], zb[K];
       if (g_tab & 4096) {  // (debug ablation: no reductions)
@@ -1329,8 +1384,8 @@ __global__ __launch_bounds__(TB) void train_step(TrainArgs a, int cb, int gb, in
         P += sa[k];
         Q += sb[k];
       }
-      P = P / (float)K;
-      Q = Q / (float)K;
+      P = div_k<K>(P);
+      Q = div_k<K>(Q);
       const float y3 = mul_nc(P, Q);
       float l1, l2, l3, g1, g2, g3;
       head_loss_nc(lossk, y1, yt0, l1, g1);
@@ -1343,7 +1398,7 @@ __global__ __launch_bounds__(TB) void train_step(TrainArgs a, int cb, int gb, in
       g3 *= inv_b;
       const float dz1 = g1 * act_d_nc(act, z1, y1);
       const float dz2 = g2 * act_d_nc(act, z2, y2);
-      const float dP = g3 * Q / (float)K, dQ = g3 * P / (float)K;
+      const float dP = div_k<K>(g3 * Q), dQ = div_k<K>(g3 * P);
       auto emit = [&](int s, V g) {
         const unsigned cd = code[s];
         const bool edge = slot_is_edge(s, K);

@@ -92,6 +92,9 @@ def main():
   # further builds: AB_LIBS=NAME=PATH,...
   for t in filter(None, os.environ.get("AB_LIBS", "").split(",")):
     libs[t.split("=")[0]] = os.path.join(ROOT, t.split("=")[1])
+  if os.environ.get("AB_ARMS"):  # only the libraries the named arms use (and AB)
+    used = {t.split(":")[1] for t in os.environ["AB_ARMS"].split(",")} | {"AB"}
+    libs = {k: v for k, v in libs.items() if k in used}
   procs = {}
   for name, path in libs.items():
     env = dict(os.environ)

@@ -7,6 +7,10 @@ cd "$(dirname "$0")/.."
 name=$1; src=$2; flags=$3
 mkdir -p tools/_ab
 python -m hypergraphembedding_amd.build > /dev/null
+# the source's own flags of build.py (VARIANT_NO_EXTRA=1: without them)
+if [ -z "$VARIANT_NO_EXTRA" ]; then
+  flags="$(python -c "from hypergraphembedding_amd.build import EXTRA_FLAGS; print(' '.join(EXTRA_FLAGS.get('$(basename $src)', [])))") $flags"
+fi
 objs=""
 for o in hypergraphembedding_amd/_build/*.o; do
   if [ "$(basename $o)" = "$(basename $src).o" ]; then
