@@ -51,6 +51,7 @@
 #include <vector>
 
 #include "hgx_internal.h"
+#include "hgx_sample_mode.h"
 
 namespace {
 
@@ -820,8 +821,7 @@ __global__ __launch_bounds__(kSB) void reject_rows(RejectArgs A) {
     int mode = 0;
     if (A.levels == 3)
       mode = (A.mode3 == 2 ||
-              (A.mode3 == 0 && (A.mode3_shift >= 0 ? W >= ((long long)A.ncols << A.mode3_shift)
-                                                   : (W << -A.mode3_shift) >= (long long)A.ncols)))
+              (A.mode3 == 0 && sample_mode3_uniform(W, A.ncols, A.mode3_shift)))
                  ? 2
                  : 1;
     const bool small = n1 <= kSB;

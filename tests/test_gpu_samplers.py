@@ -11,6 +11,13 @@ is checked on everything that is NOT random plus the distribution:
   * HOBE probabilities of every record equal the oracle's for that pair
     (bit-exact given the same coordinates);
   * uniformity of the chosen subset (chi-square over seeds).
+
+The keyed stream itself is checked exactly elsewhere: tests/sampler_cases.py
+restates the sampler on the host, tests/test_gpu_sampler_kernels.py requires
+the device's records to equal that restatement on graphs that reach every
+kernel branch, and tests/test_sampler_cases_cpu.py tests the restatement's
+uniformity (with the statistic corrected for subsets without replacement;
+the plain chi-square used below reads about (1 - q / |row|) of it).
 """
 
 import numpy as np
