@@ -48,6 +48,7 @@ from .auto_encoder import EmbedAutoEncoder, auto_encoder_incidence
 from .node2vec import (EmbedNode2VecBipartide, EmbedNode2VecClique,
                        node2vec_incidence)
 from .deepwalk import EmbedDeepWalk, deepwalk_incidence
+from .line import EmbedLine, line_incidence
 
 __all__ = [
     # proto
@@ -65,6 +66,8 @@ __all__ = [
     "EmbedNode2VecBipartide", "EmbedNode2VecClique", "node2vec_incidence",
     # DeepWalk baseline (the "deepwalk" key)
     "EmbedDeepWalk", "deepwalk_incidence",
+    # LINE baseline (the "LINE" key)
+    "EmbedLine", "line_incidence",
     # hot-path pieces
     "BooleanSamples", "AlgebraicDistanceSamples", "SamplesToModelInput",
     "SimilarityRecord", "UniformWeight", "WeightByNeighborhood",

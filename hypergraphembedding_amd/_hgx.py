@@ -192,6 +192,10 @@ SIGNATURES = {
     "hgx_n2v_train_hs": (_int, [_vp, _i64, _int, _vp, _int, _int, _f32, _f32,
                                 _u64, _int]),
     "hgx_n2v_last_hs_stats": (_int, [_vp, _pi64]),
+    "hgx_n2v_set_arcs": (_int, [_vp, _vp, _vp, _vp]),
+    "hgx_n2v_line_samples": (_int, [_vp, _i64, _i64, _int, _u64, _vp]),
+    "hgx_n2v_train_line": (_int, [_vp, _int, _int, _i64, _f32, _u64, _int]),
+    "hgx_n2v_last_line_stats": (_int, [_vp, _pi64, _pi64, _pi64]),
     "hgx_pyrandom_sample_missing": (_int, [_vp, _i32, _i32, _vp, _vp, _i64,
                                            _vp, _vp, _pi64]),
     "hgx_pyrandom_remove_connections": (_int, [_vp, _i64, _vp, _vp, _vp, _vp,
@@ -308,7 +312,8 @@ class Context:
     waves with 1 record per workgroup there, 0 off, -1 per geometry),
     train_prep_overlap, train_prep_cus, alg_long, alg_ks,
     alg_push, mlp_fuse_head, mlp_prefetch, mlp_wgrad_split, svc_lds_m,
-    ae_chunk_rows, n2v_expand_w, n2v_chunk_walks, dw_hot_levels, stream_cus."""
+    ae_chunk_rows, n2v_expand_w, n2v_chunk_walks, dw_hot_levels,
+    line_chunk_samples, stream_cus."""
     self._chk(lib().hgx_set_tuning(self.h, key.encode(), int(value)))
 
   # ---- incidence ----
@@ -1190,17 +1195,50 @@ class N2v:
                                          int(seed) & (2**64 - 1),
                                          1 if concurrent else 0))
 
+  def set_arcs(self, thr, alias, cum):
+    """LINE's tables (line.alias_table over the incidences, both None for
+    equal weights, and the negatives' cumulative table; hgx_n2v_set_arcs)."""
+    thr = None if thr is None else _c(thr, np.uint32).ravel()
+    alias = None if alias is None else _c(alias, np.int32).ravel()
+    cum = _c(cum, np.int32).ravel()
+    assert cum.size == self.V
+    assert all(t is None or t.size == self.ctx.inc.nnz for t in (thr, alias))
+    self.ctx._chk(lib().hgx_n2v_set_arcs(self.h, _ptr(thr), _ptr(alias),
+                                         _ptr(cum)))
+
+  def line_samples(self, s0, count, negative, seed):
+    """(count, 2 + negative) int32: (u, v, negatives) of the samples s0,
+    s0 + 1, ... (hgx_n2v_line_samples)."""
+    out = np.empty((int(count), 2 + max(int(negative), 0)), np.int32)
+    self.ctx._chk(lib().hgx_n2v_line_samples(self.h, int(s0), int(count),
+                                             int(negative),
+                                             int(seed) & (2**64 - 1),
+                                             _ptr(out)))
+    return out
+
+  def train_line(self, order, negative, n_samples, rho=0.025, seed=0,
+                 concurrent=True):
+    """LINE of ``order`` 1 or 2 over ``n_samples`` edge samples
+    (hgx_n2v_train_line)."""
+    self.ctx._chk(lib().hgx_n2v_train_line(self.h, int(order), int(negative),
+                                           int(n_samples), rho,
+                                           int(seed) & (2**64 - 1),
+                                           1 if concurrent else 0))
+
   def stats(self):
     wm, tm = ctypes.c_double(), ctypes.c_double()
-    v = [ctypes.c_int64() for _ in range(6)]
+    v = [ctypes.c_int64() for _ in range(9)]
     self.ctx._chk(lib().hgx_n2v_last_stats(self.h, ctypes.byref(wm),
                                            ctypes.byref(tm),
                                            *[ctypes.byref(x) for x in v[:5]]))
     self.ctx._chk(lib().hgx_n2v_last_hs_stats(self.h, ctypes.byref(v[5])))
+    self.ctx._chk(lib().hgx_n2v_last_line_stats(
+        self.h, *[ctypes.byref(x) for x in v[6:]]))
     return {"walk_ms": wm.value, "train_ms": tm.value, "walks": v[0].value,
             "words": v[1].value, "pairs": v[2].value,
             "expand_steps": v[3].value, "reject_steps": v[4].value,
-            "path_nodes": v[5].value}
+            "path_nodes": v[5].value, "samples": v[6].value,
+            "targets": v[7].value, "clamped": v[8].value}
 
 
 # ---- host utilities (no context, no device) --------------------------------

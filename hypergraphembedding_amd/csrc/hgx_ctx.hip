@@ -180,6 +180,10 @@ extern "C" int hgx_set_tuning(hgx_ctx *ctx, const char *key, int64_t value) {
   } else if (k == "dw_hot_levels") {
     HGX_CHECK(ctx, value >= 0 && value <= 6, HGX_EINVAL, "dw_hot_levels must be in [0, 6]");
     t.dw_hot_levels = (int)value;
+  } else if (k == "line_chunk_samples") {
+    HGX_CHECK(ctx, value >= 0 && value <= (1 << 20), HGX_EINVAL,
+              "line_chunk_samples must be in [0, 2^20]");
+    t.line_chunk_samples = (int)value;
   } else if (k == "train_prep_overlap") {
     HGX_CHECK(ctx, value >= 0 && value <= 2, HGX_EINVAL, "train_prep_overlap must be 0, 1 or 2");
     t.train_prep_overlap = (int)value;

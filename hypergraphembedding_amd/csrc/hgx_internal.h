@@ -109,6 +109,8 @@ struct Tuning {
   // whose rows a workgroup sums in LDS, 0 to 6 (0: every update a global
   // atomic). 6 measured fastest at every row width
   int dw_hot_levels = 6;
+  // LINE concurrent trainer: samples per launch (0: from the vertex count)
+  int line_chunk_samples = 0;
 };
 
 struct hgx_ctx {

@@ -18,6 +18,10 @@
 //                    over the same walks, keeps and windows: per pair the
 //                    inner nodes of the output word's Huffman path, root
 //                    first, their rows of syn1 loaded kHsBatch per round trip
+//   n2v_train_line   LINE's edge-sampling trainer, first and second order
+//                    (DESIGN §4.12): no corpus, one wave per 64 consecutive
+//                    samples, the arc by alias table and the negatives drawn
+//                    by all lanes at once, one update per sample
 //
 // Either trainer has two modes. Sequential: one wave trains the walks in corpus
 // order with plain loads and stores; this is the definition of the result.
@@ -601,6 +605,215 @@ TrainFn train_kernel(int npl) {
   }
 }
 
+// ---- LINE: edge-sampling trainer ---------------------------------------------
+// Sample s (64 bits) has key(seed, s) and the counters 0 the position p0 below
+// nnz, 1 the alias decision (a 32-bit value against thr[p0]), 2 the direction,
+// 3 + k negative k. Incidence p of the node-major CSR is the two arcs row(p) ->
+// N + col_n[p] and back; row(p) is a binary search of rp_n, no arc array.
+constexpr int kSeqSamples = 8192;  // samples per launch of the sequential trainer
+
+struct LineArgs {
+  float *syn0, *tgt;  // tgt: syn0 at order 1, syn1 at order 2
+  const int *rp_n, *col_n;
+  const unsigned *thr;  // null: equal weights, no table
+  const int *alias, *cum;
+  unsigned long long *stats;  // kStatSlots x {samples, targets, clamped}
+  int dp, N, V, negative;
+  uint32_t nnz, cum_last;
+  int64_t T;
+  uint64_t seed;
+  double rho0;
+};
+
+// The draws of sample s: the arc u -> v and the negatives (-1 past A.negative)
+__device__ __forceinline__ void line_draw(const LineArgs &A, int64_t s, int &u, int &v,
+                                          int (&ng)[kMaxNeg]) {
+  const uint64_t key = hgx::rand64_key(A.seed, (uint64_t)s);
+  int p = (int)hgx::bounded(hgx::mix64(key), A.nnz);
+  if (A.thr) {
+    const uint32_t a = hgx::bounded(hgx::mix64(key + 1), 0xFFFFFFFFu);
+    if (!(a < A.thr[p])) p = A.alias[p];
+  }
+  const bool back = hgx::bounded(hgx::mix64(key + 2), 2u) != 0;
+  int lo = 0, hi = A.N;  // the first row that starts after p (rp_n[N] = nnz > p)
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (A.rp_n[mid] <= p) lo = mid + 1; else hi = mid;
+  }
+  const int nd = lo - 1, ed = A.N + A.col_n[p];
+  u = back ? ed : nd;
+  v = back ? nd : ed;
+#pragma unroll
+  for (int k = 0; k < kMaxNeg; k++) {
+    ng[k] = -1;
+    if (k < A.negative) {
+      const int x = (int)hgx::bounded(hgx::mix64(key + 3 + k), A.cum_last);
+      int l = 0, h = A.V - 1;  // x < cum[V - 1]: the answer is at most V - 1
+      while (l < h) {
+        const int mid = (l + h) >> 1;
+        if (A.cum[mid] < x) l = mid + 1; else h = mid;
+      }
+      ng[k] = l;
+    }
+  }
+}
+
+// rho of sample s: linear in s, never below 1e-4 rho0
+__device__ __forceinline__ float line_rho(const LineArgs &A, int64_t s) {
+  const double a = A.rho0 * (1.0 - (double)s / (double)(A.T + 1)), m = 1e-4 * A.rho0;
+  return (float)(a > m ? a : m);
+}
+
+__global__ void n2v_line_samples(LineArgs A, int64_t s0, int64_t count, int *out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  int u, v, ng[kMaxNeg];
+  line_draw(A, s0 + i, u, v, ng);
+  int *o = out + i * (2 + A.negative);
+  o[0] = u;
+  o[1] = v;
+#pragma unroll
+  for (int k = 0; k < kMaxNeg; k++)
+    if (k < A.negative) o[2 + k] = ng[k];
+}
+
+// One sample: l1 = syn0[u] held fixed, the targets tg[0] = v (label 1) and the
+// negatives (label 0) in order, none rejected. All rows are loaded together; a
+// target that repeats an earlier one takes that one's updated registers, and
+// so does the closing row of u at order 1 when a target was u itself.
+// Returns the number of targets with |x| > 6.
+template <int NPL, bool CONC>
+__device__ __forceinline__ int line_step(const LineArgs &A, int lane, int u, const int (&tg)[kMaxT],
+                                         float rho) {
+  const int nt = 1 + A.negative;
+  float *r0 = A.syn0 + (size_t)u * A.dp + lane;
+  float l1[NPL], err[NPL], r[kMaxT][NPL];
+#pragma unroll
+  for (int q = 0; q < NPL; q++) {
+    l1[q] = row_load<CONC>(r0 + 64 * q);
+    err[q] = 0.f;
+  }
+#pragma unroll
+  for (int k = 0; k < kMaxT; k++) {
+    if (k < nt) {
+      const float *s = A.tgt + (size_t)tg[k] * A.dp + lane;
+#pragma unroll
+      for (int q = 0; q < NPL; q++) r[k][q] = row_load<CONC>(s + 64 * q);
+    }
+  }
+  int clamped = 0;
+#pragma unroll
+  for (int k = 0; k < kMaxT; k++) {
+    if (k < nt) {
+#pragma unroll
+      for (int j = 0; j < k; j++) {
+        if (tg[j] == tg[k]) {
+#pragma unroll
+          for (int q = 0; q < NPL; q++) r[k][q] = r[j][q];
+        }
+      }
+      float x = 0.f;
+#pragma unroll
+      for (int q = 0; q < NPL; q++) x += l1[q] * r[k][q];
+      x = hgx::group_allreduce_sum<64>(x);
+      // LINE's bounded sigmoid: 1 above 6, 0 below -6, the logistic between
+      double sg;
+      if (x > 6.0f) sg = 1.0;
+      else if (x < -6.0f) sg = 0.0;
+      else sg = 1.0 / (1.0 + exp(-(double)x));
+      clamped += fabsf(x) > 6.0f;
+      const float g = (float)((k == 0 ? 1.0 : 0.0) - sg) * rho;
+      if (g != 0.f) {
+        float *s = A.tgt + (size_t)tg[k] * A.dp + lane;
+#pragma unroll
+        for (int q = 0; q < NPL; q++) {
+          err[q] += g * r[k][q];
+          const float dlt = g * l1[q];
+          r[k][q] += dlt;
+          if (CONC) unsafeAtomicAdd(s + 64 * q, dlt);
+          else s[64 * q] = r[k][q];
+        }
+      }
+    }
+  }
+  if (CONC) {
+#pragma unroll
+    for (int q = 0; q < NPL; q++) unsafeAtomicAdd(r0 + 64 * q, err[q]);
+  } else {
+    // the row of u as it now stands: at order 1 a target equal to u moved it
+    if (A.tgt == A.syn0) {
+#pragma unroll
+      for (int k = 0; k < kMaxT; k++) {
+        if (k < nt && tg[k] == u) {
+#pragma unroll
+          for (int q = 0; q < NPL; q++) l1[q] = r[k][q];
+        }
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < NPL; q++) r0[64 * q] = l1[q] + err[q];
+  }
+  return clamped;
+}
+
+// The n <= 64 consecutive samples from s0 on one wave: lane l draws sample
+// s0 + l (all lanes at once, a binary search of rp_n and one of the cumulative
+// table per negative each), then the wave trains them in order, reading lane
+// i's draws by v_readlane.
+template <int NPL, bool CONC>
+__device__ __forceinline__ void line_run(const LineArgs &A, int lane, int64_t s0, int n) {
+  int u = 0, v = 0, ng[kMaxNeg];
+#pragma unroll
+  for (int k = 0; k < kMaxNeg; k++) ng[k] = -1;
+  float rho = 0.f;
+  if (lane < n) {
+    line_draw(A, s0 + lane, u, v, ng);
+    rho = line_rho(A, s0 + lane);
+  }
+  int clamped = 0;
+  for (int i = 0; i < n; i++) {
+    int tg[kMaxT];
+    const int ui = __builtin_amdgcn_readlane(u, i);
+    tg[0] = __builtin_amdgcn_readlane(v, i);
+#pragma unroll
+    for (int k = 0; k < kMaxNeg; k++) tg[1 + k] = __builtin_amdgcn_readlane(ng[k], i);
+    const float ri =
+        __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rho), i));
+    clamped += line_step<NPL, CONC>(A, lane, ui, tg, ri);
+  }
+  if (lane == 0) {
+    unsigned long long *st = A.stats + 3 * ((s0 >> 6) % kStatSlots);
+    atomicAdd(st, (unsigned long long)n);
+    atomicAdd(st + 1, (unsigned long long)n * (1 + A.negative));
+    atomicAdd(st + 2, (unsigned long long)clamped);
+  }
+}
+
+// Concurrent: wave g of the launch trains the samples from s0 + 64 g, at most
+// 64 and none at or past s1. Sequential (one wave in all): [s0, s1) in order.
+template <int NPL, bool CONC>
+__global__ __launch_bounds__(256) void n2v_train_line(LineArgs A, int64_t s0, int64_t s1) {
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (CONC) {
+    const int64_t b = s0 + 64 * ((int64_t)blockIdx.x * 4 + wv);
+    if (b < s1) line_run<NPL, true>(A, lane, b, (int)std::min<int64_t>(64, s1 - b));
+  } else {
+    for (int64_t b = s0; b < s1; b += 64)
+      line_run<NPL, false>(A, lane, b, (int)std::min<int64_t>(64, s1 - b));
+  }
+}
+
+using LineFn = void (*)(LineArgs, int64_t, int64_t);
+template <bool CONC>
+LineFn line_kernel(int npl) {
+  switch (npl) {
+    case 1: return n2v_train_line<1, CONC>;
+    case 2: return n2v_train_line<2, CONC>;
+    case 4: return n2v_train_line<4, CONC>;
+    default: return n2v_train_line<8, CONC>;
+  }
+}
+
 }  // namespace
 
 struct hgx_n2v {
@@ -619,6 +832,11 @@ struct hgx_n2v {
   double walk_ms = 0, train_ms = 0;
   int64_t st_walks = 0, st_words = 0, st_pairs = 0, st_expand = 0, st_reject = 0;
   int64_t st_path_nodes = 0;  // of the last hgx_n2v_train_hs
+  // LINE (hgx_n2v_set_arcs / hgx_n2v_train_line)
+  DevBuf arc_thr, arc_alias, arc_cum, arc_out;
+  bool arcs = false, arc_weighted = false, vectors = false;
+  uint32_t arc_cum_last = 0;
+  int64_t st_line_samples = 0, st_line_targets = 0, st_line_clamped = 0;
 };
 
 namespace {
@@ -657,7 +875,8 @@ extern "C" int hgx_n2v_destroy(hgx_n2v *a) {
   if (!a) return HGX_OK;
   if (a->ctx) hipStreamSynchronize(a->ctx->stream);
   for (DevBuf *b : {&a->syn0, &a->syn1, &a->walks, &a->pass, &a->src, &a->count, &a->keep,
-                    &a->cum, &a->stats, &a->pstats, &a->ptr, &a->point, &a->code, &a->hot_row})
+                    &a->cum, &a->stats, &a->pstats, &a->ptr, &a->point, &a->code, &a->hot_row,
+                    &a->arc_thr, &a->arc_alias, &a->arc_cum, &a->arc_out})
     hgx_release(*b);
   for (hipEvent_t e : {a->e0, a->e1})
     if (e) hipEventDestroy(e);
@@ -870,7 +1089,9 @@ static int n2v_vectors_io(hgx_n2v *a, float *syn0, float *syn1, bool set) {
 extern "C" int hgx_n2v_set_vectors(hgx_n2v *a, const float *syn0, const float *syn1) {
   if (!a) return HGX_EINVAL;
   HGX_CHECK(a->ctx, syn0, HGX_EINVAL, "hgx_n2v_set_vectors: null syn0");
-  return n2v_vectors_io(a, const_cast<float *>(syn0), const_cast<float *>(syn1), true);
+  HGX_TRY(n2v_vectors_io(a, const_cast<float *>(syn0), const_cast<float *>(syn1), true));
+  a->vectors = true;
+  return HGX_OK;
 }
 extern "C" int hgx_n2v_get_vectors(hgx_n2v *a, float *syn0, float *syn1) {
   if (!a) return HGX_EINVAL;
@@ -1037,6 +1258,7 @@ int n2v_train_any(hgx_n2v *a, bool hs, int64_t n_walks, int walk_length, const i
     a->st_path_nodes += (int64_t)st[2 * kStatSlots + i];
   }
   a->st_walks = (int64_t)nw * epochs;
+  a->st_line_samples = a->st_line_targets = a->st_line_clamped = 0;
   return HGX_OK;
 }
 
@@ -1056,6 +1278,169 @@ extern "C" int hgx_n2v_train_hs(hgx_n2v *a, int64_t n_walks, int walk_length,
   if (!a) return HGX_EINVAL;
   return n2v_train_any(a, true, n_walks, walk_length, walks, window, 0, epochs, alpha, min_alpha,
                        seed, concurrent);
+}
+
+// ---- LINE ----------------------------------------------------------------------
+namespace {
+
+// samples per launch of the concurrent LINE trainer: the tuning value, else
+// V / 4 rounded down to a multiple of 256 (one workgroup trains 256), in
+// [256, 65536]
+int64_t line_chunk(const hgx_n2v *a) {
+  int64_t ch = a->ctx->tune.line_chunk_samples;
+  if (ch <= 0) ch = std::min(65536, std::max(256, a->V / 4 / 256 * 256));
+  return ch;
+}
+
+int line_args(hgx_n2v *a, const char *fn, int negative, LineArgs *A) {
+  hgx_ctx *ctx = a->ctx;
+  HGX_CHECK(ctx, a->graph == 0, HGX_ESTATE, "%s: the engine is not on the bipartite graph", fn);
+  HGX_CHECK(ctx, negative >= 0, HGX_EINVAL, "%s: negative %d < 0", fn, negative);
+  HGX_CHECK(ctx, negative <= kMaxNeg, HGX_EUNSUP, "%s: negative %d above %d", fn, negative,
+            kMaxNeg);
+  HGX_CHECK(ctx, a->arcs, HGX_ESTATE, "%s before hgx_n2v_set_arcs", fn);
+  A->syn0 = a->syn0.as<float>();
+  A->tgt = a->syn1.as<float>();
+  A->rp_n = ctx->rp_n.as<int>();
+  A->col_n = ctx->col_n.as<int>();
+  A->thr = a->arc_weighted ? a->arc_thr.as<unsigned>() : nullptr;
+  A->alias = a->arc_alias.as<int>();
+  A->cum = a->arc_cum.as<int>();
+  A->stats = a->stats.as<unsigned long long>();
+  A->dp = a->dp;
+  A->N = a->N;
+  A->V = a->V;
+  A->negative = negative;
+  A->nnz = (uint32_t)ctx->nnz;
+  A->cum_last = a->arc_cum_last;
+  A->T = 0;
+  A->seed = 0;
+  A->rho0 = 0.0;
+  return HGX_OK;
+}
+
+}  // namespace
+
+extern "C" int hgx_n2v_set_arcs(hgx_n2v *a, const uint32_t *thr, const int32_t *alias,
+                                const int32_t *cum) {
+  if (!a) return HGX_EINVAL;
+  hgx_ctx *ctx = a->ctx;
+  HGX_TRY(n2v_live(a));
+  HGX_CHECK(ctx, a->graph == 0, HGX_ESTATE,
+            "hgx_n2v_set_arcs: the engine is not on the bipartite graph");
+  const int64_t nnz = ctx->nnz;
+  HGX_CHECK(ctx, nnz >= 1, HGX_EINVAL, "hgx_n2v_set_arcs: an incidence without an entry");
+  HGX_CHECK(ctx, nnz < (1ll << 31), HGX_EUNSUP, "hgx_n2v_set_arcs: nnz does not fit 31 bits");
+  HGX_CHECK(ctx, cum, HGX_EINVAL, "hgx_n2v_set_arcs: null cumulative table");
+  HGX_CHECK(ctx, (thr == nullptr) == (alias == nullptr), HGX_EINVAL,
+            "hgx_n2v_set_arcs: thr and alias are given together or not at all");
+  if (alias)
+    for (int64_t p = 0; p < nnz; p++)
+      HGX_CHECK(ctx, alias[p] >= 0 && alias[p] < nnz, HGX_EINVAL,
+                "hgx_n2v_set_arcs: alias %d at position %lld outside [0, %lld)", alias[p],
+                (long long)p, (long long)nnz);
+  for (int v = 0; v < a->V; v++)
+    HGX_CHECK(ctx, cum[v] >= (v ? cum[v - 1] : 0), HGX_EINVAL,
+              "hgx_n2v_set_arcs: the cumulative table decreases at %d", v);
+  HGX_CHECK(ctx, cum[a->V - 1] > 0, HGX_EINVAL, "hgx_n2v_set_arcs: an empty cumulative table");
+  HGX_TRY(hgx_ensure(ctx, a->arc_thr, sizeof(uint32_t) * (size_t)nnz));
+  HGX_TRY(hgx_ensure(ctx, a->arc_alias, sizeof(int32_t) * (size_t)nnz));
+  HGX_TRY(hgx_ensure(ctx, a->arc_cum, sizeof(int32_t) * (size_t)a->V));
+  a->arcs = false;
+  if (thr) {
+    HGX_HIP(ctx, hipMemcpyAsync(a->arc_thr.p, thr, sizeof(uint32_t) * (size_t)nnz,
+                                hipMemcpyHostToDevice, ctx->stream));
+    HGX_HIP(ctx, hipMemcpyAsync(a->arc_alias.p, alias, sizeof(int32_t) * (size_t)nnz,
+                                hipMemcpyHostToDevice, ctx->stream));
+  }
+  HGX_HIP(ctx, hipMemcpyAsync(a->arc_cum.p, cum, sizeof(int32_t) * (size_t)a->V,
+                              hipMemcpyHostToDevice, ctx->stream));
+  HGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  a->arc_weighted = thr != nullptr;
+  a->arc_cum_last = (uint32_t)cum[a->V - 1];
+  a->arcs = true;
+  return HGX_OK;
+}
+
+extern "C" int hgx_n2v_line_samples(hgx_n2v *a, int64_t s0, int64_t count, int negative,
+                                    uint64_t seed, int32_t *out) {
+  if (!a) return HGX_EINVAL;
+  hgx_ctx *ctx = a->ctx;
+  HGX_TRY(n2v_live(a));
+  LineArgs A;
+  HGX_TRY(line_args(a, "hgx_n2v_line_samples", negative, &A));
+  HGX_CHECK(ctx, s0 >= 0 && count >= 0, HGX_EINVAL,
+            "hgx_n2v_line_samples: first sample %lld or count %lld below 0", (long long)s0,
+            (long long)count);
+  HGX_CHECK(ctx, count == 0 || out, HGX_EINVAL, "hgx_n2v_line_samples: null output");
+  HGX_CHECK(ctx, count * (2 + negative) < (1ll << 31), HGX_EUNSUP,
+            "hgx_n2v_line_samples: %lld samples of %d vertices do not fit 31 bits",
+            (long long)count, 2 + negative);
+  if (count == 0) return HGX_OK;
+  A.seed = seed;
+  const size_t bytes = sizeof(int32_t) * (size_t)count * (2 + negative);
+  HGX_TRY(hgx_ensure(ctx, a->arc_out, bytes));
+  hipLaunchKernelGGL(n2v_line_samples, dim3((unsigned)((count + 255) / 256)), dim3(256), 0,
+                     ctx->stream, A, s0, count, a->arc_out.as<int>());
+  HGX_LAUNCH_CHECK(ctx);
+  HGX_HIP(ctx, hipMemcpyAsync(out, a->arc_out.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return HGX_OK;
+}
+
+extern "C" int hgx_n2v_train_line(hgx_n2v *a, int order, int negative, int64_t n_samples,
+                                  float rho, uint64_t seed, int concurrent) {
+  if (!a) return HGX_EINVAL;
+  hgx_ctx *ctx = a->ctx;
+  const char *fn = "hgx_n2v_train_line";
+  HGX_TRY(n2v_live(a));
+  HGX_CHECK(ctx, a->graph == 0, HGX_ESTATE, "%s: the engine is not on the bipartite graph", fn);
+  HGX_CHECK(ctx, order == 1 || order == 2, HGX_EINVAL, "%s: order %d is not 1 or 2", fn, order);
+  HGX_CHECK(ctx, n_samples >= 0, HGX_EINVAL, "%s: %lld samples", fn, (long long)n_samples);
+  HGX_CHECK(ctx, concurrent == 0 || concurrent == 1, HGX_EINVAL, "%s: concurrent %d is not 0 or 1",
+            fn, concurrent);
+  LineArgs A;
+  HGX_TRY(line_args(a, fn, negative, &A));
+  HGX_CHECK(ctx, a->vectors, HGX_ESTATE, "%s before hgx_n2v_set_vectors", fn);
+  if (order == 1) A.tgt = A.syn0;
+  A.T = n_samples;
+  A.seed = seed;
+  A.rho0 = (double)rho;
+  const int npl = a->dp / 64;
+  const LineFn kern = concurrent ? line_kernel<true>(npl) : line_kernel<false>(npl);
+  HGX_HIP(ctx, hipMemsetAsync(a->stats.p, 0, a->stats.bytes, ctx->stream));
+  HGX_HIP(ctx, hipEventRecord(a->e0, ctx->stream));
+  // sequential: one wave, the samples in order, a launch per kSeqSamples so
+  // that no kernel runs long (the order, and so every bit, is the same).
+  // concurrent: a chunk of samples per launch, 64 to a wave, 4 waves to a
+  // workgroup; the launch boundary makes every update visible to the next
+  const int64_t step = concurrent ? line_chunk(a) : kSeqSamples;
+  for (int64_t s0 = 0; s0 < n_samples; s0 += step) {
+    const int64_t s1 = std::min(n_samples, s0 + step);
+    const unsigned nb = concurrent ? (unsigned)((s1 - s0 + 255) / 256) : 1u;
+    hipLaunchKernelGGL(kern, dim3(nb), dim3(concurrent ? 256 : 64), 0, ctx->stream, A, s0, s1);
+    HGX_LAUNCH_CHECK(ctx);
+  }
+  HGX_TRY(n2v_elapsed(a, &a->train_ms));
+  unsigned long long st[3 * kStatSlots];
+  HGX_HIP(ctx, hipMemcpy(st, a->stats.p, sizeof(st), hipMemcpyDeviceToHost));
+  a->st_line_samples = a->st_line_targets = a->st_line_clamped = 0;
+  for (int i = 0; i < kStatSlots; i++) {
+    a->st_line_samples += (int64_t)st[3 * i];
+    a->st_line_targets += (int64_t)st[3 * i + 1];
+    a->st_line_clamped += (int64_t)st[3 * i + 2];
+  }
+  a->st_words = a->st_pairs = a->st_path_nodes = 0;
+  return HGX_OK;
+}
+
+extern "C" int hgx_n2v_last_line_stats(const hgx_n2v *a, int64_t *samples, int64_t *targets,
+                                       int64_t *clamped) {
+  if (!a) return HGX_EINVAL;
+  if (samples) *samples = a->st_line_samples;
+  if (targets) *targets = a->st_line_targets;
+  if (clamped) *clamped = a->st_line_clamped;
+  return HGX_OK;
 }
 
 extern "C" int hgx_n2v_last_hs_stats(const hgx_n2v *a, int64_t *path_nodes) {

@@ -19,6 +19,8 @@ the six "N2V*" keys to them with ``walk_length`` 3, 5 and 7, and here those
 keys raise like the reference's ``method_not_supported`` (419-420).
 ``EmbedDeepWalk`` (deepwalk.py) is the device version of the external
 "deepwalk" baseline; the integrator binds that key, here it stays unsupported.
+``EmbedLine`` (line.py) is the device version of the external "LINE"
+baseline, under the same rule.
 """
 
 import logging
@@ -40,6 +42,7 @@ from .nmf import EmbedNMF, nmf_incidence
 from .node2vec import (EmbedNode2VecBipartide, EmbedNode2VecClique,
                        node2vec_incidence)
 from .deepwalk import EmbedDeepWalk, deepwalk_incidence
+from .line import EmbedLine, line_incidence
 from .svd import EmbedRandom, EmbedSvd
 
 log = logging.getLogger()
@@ -618,4 +621,5 @@ __all__ = ["Embed", "EMBEDDING_OPTIONS", "DEBUG_SUMMARY_OPTIONS",
            "EmbedSvd", "EmbedRandom", "EmbedNMF", "nmf_incidence",
            "EmbedAutoEncoder", "auto_encoder_incidence",
            "EmbedNode2VecBipartide", "EmbedNode2VecClique",
-           "node2vec_incidence", "EmbedDeepWalk", "deepwalk_incidence"]
+           "node2vec_incidence", "EmbedDeepWalk", "deepwalk_incidence",
+           "EmbedLine", "line_incidence"]

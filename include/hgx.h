@@ -135,6 +135,10 @@ int hgx_mem_info(hgx_ctx *ctx, int64_t *free_bytes, int64_t *total_bytes);
  *                      LDS and added to memory once per workgroup; 0 to 6
  *                      (default 6, measured fastest at every row width), 0 =
  *                      every update is a global atomic
+ *   "line_chunk_samples" LINE concurrent trainer: samples per launch, 64 to a
+ *                      wave (0 = a quarter of the vertex count rounded down to
+ *                      a multiple of 256, in [256, 65536], default; at most
+ *                      2^20)
  * Unknown keys and out-of-range values -> HGX_EINVAL. */
 int hgx_set_tuning(hgx_ctx *ctx, const char *key, int64_t value);
 
@@ -771,7 +775,42 @@ int hgx_ae_last_stats(const hgx_ae *a, double *ms, int64_t *samples,
  * workgroups at the next launch; no update is lost.
  * hgx_n2v_last_stats describes the last run of either trainer;
  * hgx_n2v_last_hs_stats: the sum of the path lengths over the pairs of the
- * last hgx_n2v_train_hs (0 after hgx_n2v_train). */
+ * last hgx_n2v_train_hs (0 after hgx_n2v_train).
+ *
+ * LINE is an edge-sampling trainer on the same engine, for the
+ * bipartite graph only (HGX_ESTATE on a clique engine); it reads no walks.
+ * Incidence p (position p of the node-major CSR) is the two arcs row(p) ->
+ * N + col_n[p] and back, both of weight w_p. hgx_n2v_set_arcs: the alias
+ * table over the incidences (draw p0 uniformly and a 32-bit value a below
+ * 2^32 - 1; take p0 if a < thr[p0], else alias[p0]; nnz entries each, both
+ * NULL for equal weights) and cum, the non-decreasing cumulative table of the
+ * negatives over the V vertices (hgx_n2v_set_vocab's rule). HGX_EINVAL when
+ * one of thr and alias is NULL and not the other, an alias is outside
+ * [0, nnz), cum decreases or cum[V - 1] <= 0; a failed call sets no tables.
+ *
+ * Sample s (64 bits, 0 <= s < n_samples) draws with key (seed, s): counter 0
+ * the position, 1 the alias decision, 2 the direction (0: u = row(p), v = N +
+ * col_n[p]; 1: the reverse), 3 + k negative k; negatives are kept as drawn.
+ * hgx_n2v_line_samples: the draws alone, row i of out (count x (2 +
+ * negative)) = (u, v, negatives) of sample s0 + i.
+ *
+ * hgx_n2v_train_line: Tgt = syn0 at order 1, syn1 at order 2. Per sample:
+ * l1 = syn0[u] held fixed, err = 0; for t = v (label 1), then each negative
+ * (label 0), in order: x = l1 . Tgt[t] (the row as it stands, this sample's
+ * earlier updates included), g = (label - s(x)) rho_s with s(x) = 1 above 6,
+ * 0 below -6, else 1 / (1 + exp(-x)); err += g Tgt[t]; Tgt[t] += g l1; then
+ * syn0[u] += err (to the row as it then stands). rho_s = max(rho (1 - s /
+ * (n_samples + 1)), 1e-4 rho). concurrent 0: one wave trains the samples in
+ * order (reproducible bit for bit). concurrent 1: "line_chunk_samples"
+ * samples per launch, wave g of a launch the 64 consecutive samples from the
+ * launch's start + 64 g in order, every update a float atomic add; same
+ * draws, results differ in the last bits from run to run. Needs
+ * hgx_n2v_set_arcs and hgx_n2v_set_vectors (HGX_ESTATE); order outside
+ * {1, 2}, negative < 0 or n_samples < 0 is HGX_EINVAL, negative > 8
+ * HGX_EUNSUP; n_samples = 0 trains nothing. hgx_n2v_last_stats' train_ms
+ * covers the run. hgx_n2v_last_line_stats: the samples, the evaluated
+ * targets and those of them with |x| > 6 of the last hgx_n2v_train_line (0
+ * after the other trainers). */
 typedef struct hgx_n2v hgx_n2v;
 int hgx_n2v_create(hgx_ctx *ctx, int graph, int dim, hgx_n2v **out);
 int hgx_n2v_destroy(hgx_n2v *n);
@@ -794,6 +833,14 @@ int hgx_n2v_train_hs(hgx_n2v *n, int64_t n_walks, int walk_length,
                      const int32_t *walks, int window, int epochs, float alpha,
                      float min_alpha, uint64_t seed, int concurrent);
 int hgx_n2v_last_hs_stats(const hgx_n2v *n, int64_t *path_nodes);
+int hgx_n2v_set_arcs(hgx_n2v *n, const uint32_t *thr, const int32_t *alias,
+                     const int32_t *cum);
+int hgx_n2v_line_samples(hgx_n2v *n, int64_t s0, int64_t count, int negative,
+                         uint64_t seed, int32_t *out);
+int hgx_n2v_train_line(hgx_n2v *n, int order, int negative, int64_t n_samples,
+                       float rho, uint64_t seed, int concurrent);
+int hgx_n2v_last_line_stats(const hgx_n2v *n, int64_t *samples,
+                            int64_t *targets, int64_t *clamped);
 
 /* ---- host utilities (bench / test data; not reference entry points) --- *
  * Power-law synthetic incidence of SURVEY.md §8(d) (C4/C5): node degree
