@@ -49,6 +49,7 @@ from .node2vec import (EmbedNode2VecBipartide, EmbedNode2VecClique,
                        node2vec_incidence)
 from .deepwalk import EmbedDeepWalk, deepwalk_incidence
 from .line import EmbedLine, line_incidence
+from .metapath2vec import EmbedMetapath2Vec, metapath2vec_incidence
 
 __all__ = [
     # proto
@@ -68,6 +69,8 @@ __all__ = [
     "EmbedDeepWalk", "deepwalk_incidence",
     # LINE baseline (the "LINE" key)
     "EmbedLine", "line_incidence",
+    # metapath2vec++ baseline (the "metapath2vec++" key)
+    "EmbedMetapath2Vec", "metapath2vec_incidence",
     # hot-path pieces
     "BooleanSamples", "AlgebraicDistanceSamples", "SamplesToModelInput",
     "SimilarityRecord", "UniformWeight", "WeightByNeighborhood",

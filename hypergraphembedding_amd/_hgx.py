@@ -196,6 +196,13 @@ SIGNATURES = {
     "hgx_n2v_line_samples": (_int, [_vp, _i64, _i64, _int, _u64, _vp]),
     "hgx_n2v_train_line": (_int, [_vp, _int, _int, _i64, _f32, _u64, _int]),
     "hgx_n2v_last_line_stats": (_int, [_vp, _pi64, _pi64, _pi64]),
+    "hgx_n2v_mp_walks": (_int, [_vp, _i64, _vp, _int, _int, _u64, _i64, _i64,
+                                _vp]),
+    "hgx_n2v_mp_counts": (_int, [_vp, _i64, _vp, _int, _int, _u64, _vp]),
+    "hgx_n2v_set_vocab_typed": (_int, [_vp, _vp, _vp, _int]),
+    "hgx_n2v_train_mp": (_int, [_vp, _i64, _vp, _int, _int, _int, _int, _int,
+                                _f32, _f32, _u64, _u64, _int]),
+    "hgx_n2v_last_mp_stats": (_int, [_vp, _pi64, _pi64, _pi64, _pi64, _pi64]),
     "hgx_pyrandom_sample_missing": (_int, [_vp, _i32, _i32, _vp, _vp, _i64,
                                            _vp, _vp, _pi64]),
     "hgx_pyrandom_remove_connections": (_int, [_vp, _i64, _vp, _vp, _vp, _vp,
@@ -313,7 +320,7 @@ class Context:
     train_prep_overlap, train_prep_cus, alg_long, alg_ks,
     alg_push, mlp_fuse_head, mlp_prefetch, mlp_wgrad_split, svc_lds_m,
     ae_chunk_rows, n2v_expand_w, n2v_chunk_walks, dw_hot_levels,
-    line_chunk_samples, stream_cus."""
+    line_chunk_samples, mp_chunk_walks, stream_cus."""
     self._chk(lib().hgx_set_tuning(self.h, key.encode(), int(value)))
 
   # ---- incidence ----
@@ -1225,6 +1232,56 @@ class N2v:
                                            int(seed) & (2**64 - 1),
                                            1 if concurrent else 0))
 
+  def mp_walks(self, sources, num_walks, L, walk_seed, g0, count):
+    """(count, L) int32: the walks g0 .. g0 + count - 1 of the metapath2vec
+    corpus (hgx_n2v_mp_walks)."""
+    sr = _c(sources, np.int32).ravel()
+    out = np.empty((max(int(count), 0), max(int(L), 0)), np.int32)
+    self.ctx._chk(lib().hgx_n2v_mp_walks(self.h, sr.size, _ptr(sr),
+                                         int(num_walks), int(L),
+                                         int(walk_seed) & (2**64 - 1), int(g0),
+                                         int(count), _ptr(out)))
+    return out
+
+  def mp_counts(self, sources, num_walks, L, walk_seed):
+    """Occurrences of every vertex over the streamed corpus, int64
+    (hgx_n2v_mp_counts)."""
+    sr = _c(sources, np.int32).ravel()
+    out = np.empty(self.V, np.int64)
+    self.ctx._chk(lib().hgx_n2v_mp_counts(self.h, sr.size, _ptr(sr),
+                                          int(num_walks), int(L),
+                                          int(walk_seed) & (2**64 - 1),
+                                          _ptr(out)))
+    return out
+
+  def set_vocab_typed(self, keep, cum, typed):
+    """The metapath2vec trainer's vocabulary: ``typed`` true for one segment
+    of ``cum`` per vertex type (hgx_n2v_set_vocab_typed)."""
+    keep, cum = _c(keep, np.uint32).ravel(), _c(cum, np.int32).ravel()
+    assert keep.size == cum.size == self.V
+    self.ctx._chk(lib().hgx_n2v_set_vocab_typed(self.h, _ptr(keep), _ptr(cum),
+                                                1 if typed else 0))
+
+  def train_mp(self, sources, num_walks, L, *, window=7, negative=5, epochs=5,
+               alpha=0.025, min_alpha=2.5e-6, walk_seed=0, train_seed=0,
+               concurrent=True):
+    """metapath2vec(++) over the streamed corpus (hgx_n2v_train_mp)."""
+    sr = _c(sources, np.int32).ravel()
+    self.ctx._chk(lib().hgx_n2v_train_mp(
+        self.h, sr.size, _ptr(sr), int(num_walks), int(L), int(window),
+        int(negative), int(epochs), alpha, min_alpha,
+        int(walk_seed) & (2**64 - 1), int(train_seed) & (2**64 - 1),
+        1 if concurrent else 0))
+
+  def mp_stats(self):
+    """walks, words, pairs, targets and clamped of the last train_mp
+    (hgx_n2v_last_mp_stats)."""
+    v = [ctypes.c_int64() for _ in range(5)]
+    self.ctx._chk(lib().hgx_n2v_last_mp_stats(
+        self.h, *[ctypes.byref(x) for x in v]))
+    return dict(zip(("walks", "words", "pairs", "targets", "clamped"),
+                    (x.value for x in v)))
+
   def stats(self):
     wm, tm = ctypes.c_double(), ctypes.c_double()
     v = [ctypes.c_int64() for _ in range(9)]
@@ -1238,7 +1295,8 @@ class N2v:
             "words": v[1].value, "pairs": v[2].value,
             "expand_steps": v[3].value, "reject_steps": v[4].value,
             "path_nodes": v[5].value, "samples": v[6].value,
-            "targets": v[7].value, "clamped": v[8].value}
+            "targets": v[7].value, "clamped": v[8].value,
+            "mp": self.mp_stats()}
 
 
 # ---- host utilities (no context, no device) --------------------------------

@@ -184,6 +184,10 @@ extern "C" int hgx_set_tuning(hgx_ctx *ctx, const char *key, int64_t value) {
     HGX_CHECK(ctx, value >= 0 && value <= (1 << 20), HGX_EINVAL,
               "line_chunk_samples must be in [0, 2^20]");
     t.line_chunk_samples = (int)value;
+  } else if (k == "mp_chunk_walks") {
+    HGX_CHECK(ctx, value >= 0 && value <= (1 << 16), HGX_EINVAL,
+              "mp_chunk_walks must be in [0, 65536]");
+    t.mp_chunk_walks = (int)value;
   } else if (k == "train_prep_overlap") {
     HGX_CHECK(ctx, value >= 0 && value <= 2, HGX_EINVAL, "train_prep_overlap must be 0, 1 or 2");
     t.train_prep_overlap = (int)value;

@@ -111,6 +111,10 @@ struct Tuning {
   int dw_hot_levels = 6;
   // LINE concurrent trainer: samples per launch (0: from the vertex count)
   int line_chunk_samples = 0;
+  // metapath2vec: walks per chunk of the streamed corpus, rounded up to a
+  // multiple of 4 (0: n2v_chunk_walks' rule; the sequential trainer then
+  // takes 64)
+  int mp_chunk_walks = 0;
 };
 
 struct hgx_ctx {

@@ -22,6 +22,10 @@
 //                    (DESIGN §4.12): no corpus, one wave per 64 consecutive
 //                    samples, the arc by alias table and the negatives drawn
 //                    by all lanes at once, one update per sample
+//   n2v_train_mp     metapath2vec(++)'s trainer: n2v_train over
+//                    a corpus that is generated chunk by chunk and never
+//                    resident, sentences of up to 256 vertices, negatives from
+//                    the output word's own type, LINE's clamped sigmoid
 //
 // Either trainer has two modes. Sequential: one wave trains the walks in corpus
 // order with plain loads and stores; this is the definition of the result.
@@ -814,6 +818,230 @@ LineFn line_kernel(int npl) {
   }
 }
 
+// ---- metapath2vec: streamed corpus, typed negatives ---------------------------
+// Walk g of the corpus has pass g / n_src and source sources[g % n_src]; a
+// chunk of walks is generated by n2v_walk_bip (p = 1) from the chunk's device-
+// computed (pass, source) and trained, never the whole corpus. Positions reach
+// 255, so the trainer's counter is (position i << 8 | position j) << 4 | slot.
+constexpr int kMpMaxL = 256;    // vertices of a sentence
+constexpr int kMpStage = 512;   // negatives staged per output word and wave
+constexpr int kMpSeqWalks = 64;   // default chunk of the sequential trainer
+constexpr int kMpStat = 4;      // words, pairs, targets, clamped
+
+__host__ __device__ inline uint64_t mp_ctr(int pi, int pj, int slot) {
+  return ((((uint64_t)pi << 8) | (uint64_t)pj) << 4) | (uint64_t)slot;
+}
+
+__global__ void n2v_mp_sources(int n, int g0, int n_src, const int *sources, int *pass,
+                               int *src) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int g = g0 + i;
+  pass[i] = g / n_src;
+  src[i] = sources[g % n_src];
+}
+
+__global__ void n2v_hist64(const int *walks, size_t n, unsigned long long *count) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) atomicAdd(count + walks[i], 1ull);
+}
+
+struct MpArgs {
+  float *syn0, *syn1;
+  const int *walks;  // the chunk: walk g at row g - (the launch's first walk)
+  const unsigned *keep;
+  const int *cum;
+  unsigned long long *stats;  // kStatSlots x {words, pairs, targets, clamped}
+  int dp, L, V, N, window, negative, epochs, typed;
+  int n_walks;  // of the corpus
+  uint32_t last_node, last_edge;  // typed: cum[N - 1] and cum[V - 1]
+  uint64_t seed;
+  double alpha, min_alpha;
+};
+
+// train_pair with LINE's bounded sigmoid: no target is skipped for its x; one
+// beyond +-6 whose label the clamped value equals has g = 0 and changes
+// nothing. Counts the evaluated targets and those with |x| > 6.
+template <int NPL, bool CONC>
+__device__ __forceinline__ void train_pair_mp(const MpArgs &A, int lane, int wj, int wi,
+                                              const int *negs, float alpha, int &targets,
+                                              int &clamped) {
+  const int nt = 1 + A.negative;
+  float *r0 = A.syn0 + (size_t)wj * A.dp + lane;
+  float l1[NPL], neu[NPL], r[kMaxT][NPL];
+  int tg[kMaxT];
+#pragma unroll
+  for (int k = 0; k < kMaxT; k++)
+    tg[k] = k == 0 ? wi : (k < nt ? __builtin_amdgcn_readfirstlane(negs[k - 1]) : -1);
+#pragma unroll
+  for (int q = 0; q < NPL; q++) {
+    l1[q] = row_load<CONC>(r0 + 64 * q);
+    neu[q] = 0.f;
+  }
+#pragma unroll
+  for (int k = 0; k < kMaxT; k++) {
+    if (k < nt) {
+      const float *s = A.syn1 + (size_t)tg[k] * A.dp + lane;
+#pragma unroll
+      for (int q = 0; q < NPL; q++) r[k][q] = row_load<CONC>(s + 64 * q);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kMaxT; k++) {
+    if (k < nt && (k == 0 || tg[k] != wi)) {
+#pragma unroll
+      for (int j = 0; j < k; j++) {
+        if (tg[j] == tg[k]) {
+#pragma unroll
+          for (int q = 0; q < NPL; q++) r[k][q] = r[j][q];
+        }
+      }
+      float x = 0.f;
+#pragma unroll
+      for (int q = 0; q < NPL; q++) x += l1[q] * r[k][q];
+      x = hgx::group_allreduce_sum<64>(x);
+      double sg;
+      if (x > 6.0f) sg = 1.0;
+      else if (x < -6.0f) sg = 0.0;
+      else sg = 1.0 / (1.0 + exp(-(double)x));
+      targets++;
+      clamped += fabsf(x) > 6.0f;
+      const float g = (float)((k == 0 ? 1.0 : 0.0) - sg) * alpha;
+      if (g != 0.f) {
+        float *s = A.syn1 + (size_t)tg[k] * A.dp + lane;
+#pragma unroll
+        for (int q = 0; q < NPL; q++) {
+          neu[q] += g * r[k][q];
+          const float dlt = g * l1[q];
+          r[k][q] += dlt;
+          if (CONC) unsafeAtomicAdd(s + 64 * q, dlt);
+          else s[64 * q] = r[k][q];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NPL; q++) {
+    if (CONC) unsafeAtomicAdd(r0 + 64 * q, neu[q]);
+    else r0[64 * q] = l1[q] + neu[q];
+  }
+}
+
+// walk_keeps for a sentence of up to 256 positions: four 64-lane passes
+__device__ __forceinline__ int mp_keeps(const MpArgs &A, int lane, uint64_t key, const int *walk,
+                                        volatile int *kw, volatile int *kb) {
+  int nk = 0;
+  for (int h = 0; h < kMpMaxL / 64; h++) {
+    const int pos = lane + 64 * h;
+    const bool valid = pos < A.L;
+    const int word = valid ? walk[pos] : 0;
+    bool keep = false;
+    if (valid)
+      keep = A.keep[word] > hgx::bounded(hgx::mix64(key + mp_ctr(pos, 0, 0)), 0xFFFFFFFFu);
+    const unsigned long long mask = __ballot(keep);
+    if (keep) {
+      const int idx = nk + __popcll(mask & ((1ull << lane) - 1ull));
+      const int b = (int)hgx::bounded(hgx::mix64(key + mp_ctr(pos, 0, 1)), (uint32_t)A.window);
+      const int span = min(A.window - b, kMpMaxL);
+      kw[idx] = word;
+      kb[idx] = pos | (span << 8);
+    }
+    nk += __popcll(mask);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  return nk;
+}
+
+// Walk g of epoch ep (row `row` of the chunk) on one wave. The negatives of an
+// output word's pairs, at most min(2 window + 1, L) x negative <= kMpStage,
+// come from the segment of the word's type and are drawn by all lanes at once.
+template <int NPL, bool CONC>
+__device__ __forceinline__ void train_walk_mp(const MpArgs &A, int lane, int ep, int g, int row,
+                                              volatile int *kw, volatile int *kb,
+                                              volatile int *ng) {
+  const uint64_t key = hgx::rand64_key(A.seed, ((uint64_t)(uint32_t)ep << 32) | (uint32_t)g);
+  const double gidx = (double)ep * (double)A.n_walks + (double)g;
+  const double al = A.alpha - (A.alpha - A.min_alpha) * gidx /
+                                  ((double)A.epochs * (double)A.n_walks);
+  const float alpha = (float)(al > A.min_alpha ? al : A.min_alpha);
+  const int nk = mp_keeps(A, lane, key, A.walks + (size_t)row * A.L, kw, kb);
+  long long pairs = 0, targets = 0, clamped = 0;
+  for (int i = 0; i < nk; i++) {
+    const int wi = __builtin_amdgcn_readfirstlane(kw[i]);
+    const int pbi = __builtin_amdgcn_readfirstlane(kb[i]);
+    const int pi = pbi & 255, span = pbi >> 8;
+    const int j0 = max(0, i - span), j1 = min(nk - 1, i + span);
+    const int total = (j1 - j0 + 1) * A.negative;
+    const bool edge = A.typed && wi >= A.N;
+    const int seg_lo = edge ? A.N : 0;
+    const int seg_hi = (A.typed && !edge ? A.N : A.V) - 1;
+    const uint32_t last = edge || !A.typed ? A.last_edge : A.last_node;
+    for (int s = lane; s < total; s += 64) {
+      const int j = j0 + s / A.negative, k = s % A.negative;
+      if (j == i) continue;
+      const int pj = kb[j] & 255;
+      const int x = (int)hgx::bounded(hgx::mix64(key + mp_ctr(pi, pj, 2 + k)), last);
+      int lo = seg_lo, hi = seg_hi;  // x < cum[seg_hi]: the answer is at most seg_hi
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (A.cum[mid] < x) lo = mid + 1; else hi = mid;
+      }
+      ng[s] = lo;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    for (int j = j0; j <= j1; j++) {
+      if (j == i) continue;
+      const int wj = __builtin_amdgcn_readfirstlane(kw[j]);
+      int nt = 0, nc = 0;
+      train_pair_mp<NPL, CONC>(A, lane, wj, wi, (const int *)ng + (j - j0) * A.negative, alpha,
+                               nt, nc);
+      pairs++;
+      targets += nt;
+      clamped += nc;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  if (lane == 0) {
+    unsigned long long *st = A.stats + kMpStat * (g % kStatSlots);
+    atomicAdd(st, (unsigned long long)nk);
+    atomicAdd(st + 1, (unsigned long long)pairs);
+    atomicAdd(st + 2, (unsigned long long)targets);
+    atomicAdd(st + 3, (unsigned long long)clamped);
+  }
+}
+
+// The walks [g0, g1) of epoch ep, rows 0 .. g1 - g0 - 1 of the chunk.
+// Concurrent: wave w of the launch trains walk g0 + w. Sequential (one wave in
+// all): the walks in order.
+template <int NPL, bool CONC>
+__global__ __launch_bounds__(256) void n2v_train_mp(MpArgs A, int ep, int g0, int g1) {
+  __shared__ int s_kw[4][kMpMaxL], s_kb[4][kMpMaxL], s_ng[4][kMpStage];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (CONC) {
+    const int g = g0 + blockIdx.x * 4 + wv;
+    if (g < g1) train_walk_mp<NPL, true>(A, lane, ep, g, g - g0, s_kw[wv], s_kb[wv], s_ng[wv]);
+  } else {
+    for (int g = g0; g < g1; g++)
+      train_walk_mp<NPL, false>(A, lane, ep, g, g - g0, s_kw[0], s_kb[0], s_ng[0]);
+  }
+}
+
+using MpFn = void (*)(MpArgs, int, int, int);
+template <bool CONC>
+MpFn mp_kernel(int npl) {
+  switch (npl) {
+    case 1: return n2v_train_mp<1, CONC>;
+    case 2: return n2v_train_mp<2, CONC>;
+    case 4: return n2v_train_mp<4, CONC>;
+    default: return n2v_train_mp<8, CONC>;
+  }
+}
+
 }  // namespace
 
 struct hgx_n2v {
@@ -837,6 +1065,15 @@ struct hgx_n2v {
   bool arcs = false, arc_weighted = false, vectors = false;
   uint32_t arc_cum_last = 0;
   int64_t st_line_samples = 0, st_line_targets = 0, st_line_clamped = 0;
+  // metapath2vec (hgx_n2v_set_vocab_typed / hgx_n2v_train_mp): its own
+  // vocabulary, the source list and one chunk of walks
+  DevBuf mp_keep, mp_cum, mp_sources, mp_pass, mp_src, mp_walks, mp_count, mp_stats;
+  bool mp_vocab = false;
+  int mp_typed = 0;
+  uint32_t mp_last_node = 0, mp_last_edge = 0;
+  std::vector<hipEvent_t> mp_ev;  // a ring of event pairs round the walk kernels
+  int64_t st_mp_walks = 0, st_mp_words = 0, st_mp_pairs = 0, st_mp_targets = 0,
+          st_mp_clamped = 0;
 };
 
 namespace {
@@ -876,9 +1113,13 @@ extern "C" int hgx_n2v_destroy(hgx_n2v *a) {
   if (a->ctx) hipStreamSynchronize(a->ctx->stream);
   for (DevBuf *b : {&a->syn0, &a->syn1, &a->walks, &a->pass, &a->src, &a->count, &a->keep,
                     &a->cum, &a->stats, &a->pstats, &a->ptr, &a->point, &a->code, &a->hot_row,
-                    &a->arc_thr, &a->arc_alias, &a->arc_cum, &a->arc_out})
+                    &a->arc_thr, &a->arc_alias, &a->arc_cum, &a->arc_out, &a->mp_keep,
+                    &a->mp_cum, &a->mp_sources, &a->mp_pass, &a->mp_src, &a->mp_walks,
+                    &a->mp_count, &a->mp_stats})
     hgx_release(*b);
   for (hipEvent_t e : {a->e0, a->e1})
+    if (e) hipEventDestroy(e);
+  for (hipEvent_t e : a->mp_ev)
     if (e) hipEventDestroy(e);
   delete a;
   return HGX_OK;
@@ -1460,5 +1701,262 @@ extern "C" int hgx_n2v_last_stats(const hgx_n2v *a, double *walk_ms, double *tra
   if (pairs) *pairs = a->st_pairs;
   if (expand_steps) *expand_steps = a->st_expand;
   if (reject_steps) *reject_steps = a->st_reject;
+  return HGX_OK;
+}
+
+// ---- metapath2vec ----------------------------------------------------------------
+namespace {
+
+constexpr int kMpEvPairs = 32;  // walk-kernel timings in flight
+
+// walks per chunk: the tuning value, else chunk_walks' rule (the sequential
+// trainer: kMpSeqWalks); a multiple of 4
+int mp_chunk(const hgx_n2v *a, bool sequential) {
+  int ch = a->ctx->tune.mp_chunk_walks;
+  if (ch <= 0) ch = sequential ? kMpSeqWalks : chunk_walks(a);
+  return (ch + 3) / 4 * 4;
+}
+
+// The checks every entry point shares; uploads the source list, sizes the
+// chunk buffers for `chunk` walks and returns the corpus size.
+int mp_corpus(hgx_n2v *a, const char *fn, int64_t n_src, const int32_t *sources, int num_walks,
+              int L, int chunk, int *n_walks) {
+  hgx_ctx *ctx = a->ctx;
+  HGX_CHECK(ctx, a->graph == 0, HGX_ESTATE, "%s: the engine is not on the bipartite graph", fn);
+  HGX_CHECK(ctx, L >= 1 && num_walks >= 1 && n_src >= 1 && sources, HGX_EINVAL,
+            "%s: %lld sources, %d walks per source of %d vertices", fn, (long long)n_src,
+            num_walks, L);
+  HGX_CHECK(ctx, L <= kMpMaxL, HGX_EUNSUP, "%s: %d vertices per walk above %d", fn, L, kMpMaxL);
+  HGX_CHECK(ctx, n_src * (int64_t)num_walks < (1ll << 31), HGX_EUNSUP,
+            "%s: %lld x %d walks do not fit 31 bits", fn, (long long)n_src, num_walks);
+  for (int64_t i = 0; i < n_src; i++) {
+    const int s = sources[i];
+    HGX_CHECK(ctx, s >= a->N && s < a->V, HGX_EINVAL,
+              "%s: source %d at position %lld is not an edge vertex in [%d, %d)", fn, s,
+              (long long)i, a->N, a->V);
+    HGX_CHECK(ctx, a->h_rp_e[s - a->N + 1] > a->h_rp_e[s - a->N], HGX_EINVAL,
+              "%s: source %d at position %lld is an edge without a node", fn, s, (long long)i);
+  }
+  HGX_TRY(hgx_ensure(ctx, a->mp_sources, sizeof(int) * (size_t)n_src));
+  HGX_TRY(hgx_ensure(ctx, a->mp_pass, sizeof(int) * (size_t)chunk));
+  HGX_TRY(hgx_ensure(ctx, a->mp_src, sizeof(int) * (size_t)chunk));
+  HGX_TRY(hgx_ensure(ctx, a->mp_walks, sizeof(int) * (size_t)chunk * L));
+  HGX_HIP(ctx, hipMemcpyAsync(a->mp_sources.p, sources, sizeof(int) * (size_t)n_src,
+                              hipMemcpyHostToDevice, ctx->stream));
+  *n_walks = (int)(n_src * num_walks);
+  return HGX_OK;
+}
+
+// The walks g0 .. g0 + n - 1 into the chunk buffer (n at most the chunk the
+// buffers were sized for)
+int mp_generate(hgx_n2v *a, int g0, int n, int n_src, int L, uint64_t seed) {
+  hgx_ctx *ctx = a->ctx;
+  const dim3 g((unsigned)((n + 63) / 64)), b(64);
+  hipLaunchKernelGGL(n2v_mp_sources, g, b, 0, ctx->stream, n, g0, n_src,
+                     a->mp_sources.as<int>(), a->mp_pass.as<int>(), a->mp_src.as<int>());
+  HGX_LAUNCH_CHECK(ctx);
+  hipLaunchKernelGGL(n2v_walk_bip, g, b, 0, ctx->stream, n, a->mp_pass.as<int>(),
+                     a->mp_src.as<int>(), L, 1.0, seed, a->N, ctx->rp_n.as<int>(),
+                     ctx->col_n.as<int>(), ctx->rp_e.as<int>(), ctx->col_e.as<int>(),
+                     a->mp_walks.as<int>());
+  HGX_LAUNCH_CHECK(ctx);
+  return HGX_OK;
+}
+
+}  // namespace
+
+extern "C" int hgx_n2v_mp_walks(hgx_n2v *a, int64_t n_src, const int32_t *sources, int num_walks,
+                                int L, uint64_t walk_seed, int64_t g0, int64_t count,
+                                int32_t *out) {
+  if (!a) return HGX_EINVAL;
+  hgx_ctx *ctx = a->ctx;
+  const char *fn = "hgx_n2v_mp_walks";
+  HGX_TRY(n2v_live(a));
+  const int chunk = mp_chunk(a, false);
+  int nw = 0;
+  HGX_TRY(mp_corpus(a, fn, n_src, sources, num_walks, L, chunk, &nw));
+  HGX_CHECK(ctx, g0 >= 0 && count >= 0 && g0 + count <= nw, HGX_EINVAL,
+            "%s: the walks %lld .. %lld + %lld are not all in [0, %d)", fn, (long long)g0,
+            (long long)g0, (long long)count, nw);
+  HGX_CHECK(ctx, count == 0 || out, HGX_EINVAL, "%s: null output", fn);
+  for (int64_t c0 = 0; c0 < count; c0 += chunk) {
+    const int n = (int)std::min<int64_t>(chunk, count - c0);
+    HGX_TRY(mp_generate(a, (int)(g0 + c0), n, (int)n_src, L, walk_seed));
+    HGX_HIP(ctx, hipMemcpyAsync(out + (size_t)c0 * L, a->mp_walks.p, sizeof(int) * (size_t)n * L,
+                                hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return HGX_OK;
+}
+
+extern "C" int hgx_n2v_mp_counts(hgx_n2v *a, int64_t n_src, const int32_t *sources, int num_walks,
+                                 int L, uint64_t walk_seed, int64_t *counts_out) {
+  if (!a) return HGX_EINVAL;
+  hgx_ctx *ctx = a->ctx;
+  const char *fn = "hgx_n2v_mp_counts";
+  HGX_TRY(n2v_live(a));
+  const int chunk = mp_chunk(a, false);
+  int nw = 0;
+  HGX_TRY(mp_corpus(a, fn, n_src, sources, num_walks, L, chunk, &nw));
+  HGX_CHECK(ctx, counts_out, HGX_EINVAL, "%s: null output", fn);
+  static_assert(sizeof(unsigned long long) == sizeof(int64_t), "64-bit counts");
+  HGX_TRY(hgx_ensure(ctx, a->mp_count, sizeof(int64_t) * (size_t)a->V));
+  HGX_HIP(ctx, hipMemsetAsync(a->mp_count.p, 0, sizeof(int64_t) * (size_t)a->V, ctx->stream));
+  HGX_HIP(ctx, hipEventRecord(a->e0, ctx->stream));
+  for (int64_t g0 = 0; g0 < nw; g0 += chunk) {
+    const int n = (int)std::min<int64_t>(chunk, nw - g0);
+    HGX_TRY(mp_generate(a, (int)g0, n, (int)n_src, L, walk_seed));
+    const size_t tokens = (size_t)n * L;
+    hipLaunchKernelGGL(n2v_hist64, dim3((unsigned)((tokens + 255) / 256)), dim3(256), 0,
+                       ctx->stream, a->mp_walks.as<int>(), tokens,
+                       a->mp_count.as<unsigned long long>());
+    HGX_LAUNCH_CHECK(ctx);
+  }
+  HGX_TRY(n2v_elapsed(a, &a->walk_ms));
+  HGX_HIP(ctx, hipMemcpy(counts_out, a->mp_count.p, sizeof(int64_t) * (size_t)a->V,
+                         hipMemcpyDeviceToHost));
+  return HGX_OK;
+}
+
+extern "C" int hgx_n2v_set_vocab_typed(hgx_n2v *a, const uint32_t *keep, const int32_t *cum,
+                                       int typed) {
+  if (!a) return HGX_EINVAL;
+  hgx_ctx *ctx = a->ctx;
+  const char *fn = "hgx_n2v_set_vocab_typed";
+  HGX_TRY(n2v_live(a));
+  HGX_CHECK(ctx, a->graph == 0, HGX_ESTATE, "%s: the engine is not on the bipartite graph", fn);
+  HGX_CHECK(ctx, keep && cum, HGX_EINVAL, "%s: null table", fn);
+  HGX_CHECK(ctx, typed == 0 || typed == 1, HGX_EINVAL, "%s: typed %d is not 0 or 1", fn, typed);
+  for (int v = 0; v < a->V; v++)
+    HGX_CHECK(ctx, cum[v] >= (v && !(typed && v == a->N) ? cum[v - 1] : 0), HGX_EINVAL,
+              "%s: the cumulative table decreases at %d", fn, v);
+  HGX_CHECK(ctx, cum[a->V - 1] > 0 && (!typed || cum[a->N - 1] > 0), HGX_EINVAL,
+            "%s: an empty cumulative table", fn);
+  HGX_TRY(hgx_ensure(ctx, a->mp_keep, sizeof(uint32_t) * (size_t)a->V));
+  HGX_TRY(hgx_ensure(ctx, a->mp_cum, sizeof(int32_t) * (size_t)a->V));
+  a->mp_vocab = false;
+  HGX_HIP(ctx, hipMemcpyAsync(a->mp_keep.p, keep, sizeof(uint32_t) * (size_t)a->V,
+                              hipMemcpyHostToDevice, ctx->stream));
+  HGX_HIP(ctx, hipMemcpyAsync(a->mp_cum.p, cum, sizeof(int32_t) * (size_t)a->V,
+                              hipMemcpyHostToDevice, ctx->stream));
+  HGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  a->mp_typed = typed;
+  a->mp_last_node = (uint32_t)cum[a->N - 1];
+  a->mp_last_edge = (uint32_t)cum[a->V - 1];
+  a->mp_vocab = true;
+  return HGX_OK;
+}
+
+extern "C" int hgx_n2v_train_mp(hgx_n2v *a, int64_t n_src, const int32_t *sources, int num_walks,
+                                int L, int window, int negative, int epochs, float alpha,
+                                float min_alpha, uint64_t walk_seed, uint64_t train_seed,
+                                int concurrent) {
+  if (!a) return HGX_EINVAL;
+  hgx_ctx *ctx = a->ctx;
+  const char *fn = "hgx_n2v_train_mp";
+  HGX_TRY(n2v_live(a));
+  HGX_CHECK(ctx, a->graph == 0, HGX_ESTATE, "%s: the engine is not on the bipartite graph", fn);
+  HGX_CHECK(ctx, window >= 1 && epochs >= 0 && negative >= 0, HGX_EINVAL,
+            "%s: window %d, epochs %d or negative %d out of range", fn, window, epochs, negative);
+  HGX_CHECK(ctx, concurrent == 0 || concurrent == 1, HGX_EINVAL, "%s: concurrent %d is not 0 or 1",
+            fn, concurrent);
+  HGX_CHECK(ctx, negative <= kMaxNeg, HGX_EUNSUP, "%s: negative %d above %d", fn, negative,
+            kMaxNeg);
+  const int chunk = mp_chunk(a, !concurrent);
+  int nw = 0;
+  HGX_TRY(mp_corpus(a, fn, n_src, sources, num_walks, L, chunk, &nw));
+  HGX_CHECK(ctx, (int64_t)std::min<int64_t>(2 * (int64_t)window + 1, L) * negative <= kMpStage,
+            HGX_EUNSUP, "%s: window %d with %d negatives stages more than %d negatives per word",
+            fn, window, negative, kMpStage);
+  HGX_CHECK(ctx, a->mp_vocab, HGX_ESTATE, "%s before hgx_n2v_set_vocab_typed", fn);
+  HGX_CHECK(ctx, a->vectors, HGX_ESTATE, "%s before hgx_n2v_set_vectors", fn);
+  HGX_TRY(hgx_ensure(ctx, a->mp_stats, sizeof(unsigned long long) * kMpStat * kStatSlots));
+  if (a->mp_ev.empty()) {
+    a->mp_ev.assign(2 * kMpEvPairs, nullptr);
+    for (hipEvent_t &e : a->mp_ev) HGX_HIP(ctx, hipEventCreate(&e));
+  }
+  MpArgs A;
+  A.syn0 = a->syn0.as<float>();
+  A.syn1 = a->syn1.as<float>();
+  A.walks = a->mp_walks.as<int>();
+  A.keep = a->mp_keep.as<unsigned>();
+  A.cum = a->mp_cum.as<int>();
+  A.stats = a->mp_stats.as<unsigned long long>();
+  A.dp = a->dp;
+  A.L = L;
+  A.V = a->V;
+  A.N = a->N;
+  A.window = window;
+  A.negative = negative;
+  A.epochs = epochs;
+  A.typed = a->mp_typed;
+  A.n_walks = nw;
+  A.last_node = a->mp_last_node;
+  A.last_edge = a->mp_last_edge;
+  A.seed = train_seed;
+  A.alpha = (double)alpha;
+  A.min_alpha = (double)min_alpha;
+  const int npl = a->dp / 64;
+  const MpFn kern = concurrent ? mp_kernel<true>(npl) : mp_kernel<false>(npl);
+  HGX_HIP(ctx, hipMemsetAsync(a->mp_stats.p, 0, a->mp_stats.bytes, ctx->stream));
+  HGX_HIP(ctx, hipEventRecord(a->e0, ctx->stream));
+  // per chunk: the walks into the chunk buffer, then the trainer over them.
+  // The stream orders the two, and the next chunk's walks after the trainer.
+  // The walk kernels are timed by a ring of event pairs, read kMpEvPairs
+  // chunks later so that the host does not wait on the chunk in flight.
+  double walk_ms = 0;
+  int64_t launched = 0;
+  auto collect = [&](int slot) -> int {
+    float t = 0.f;
+    HGX_HIP(ctx, hipEventSynchronize(a->mp_ev[2 * slot + 1]));
+    HGX_HIP(ctx, hipEventElapsedTime(&t, a->mp_ev[2 * slot], a->mp_ev[2 * slot + 1]));
+    walk_ms += t;
+    return HGX_OK;
+  };
+  for (int ep = 0; ep < epochs; ep++)
+    for (int64_t g0 = 0; g0 < nw; g0 += chunk) {
+      const int n = (int)std::min<int64_t>(chunk, nw - g0);
+      const int slot = (int)(launched % kMpEvPairs);
+      if (launched >= kMpEvPairs) HGX_TRY(collect(slot));
+      HGX_HIP(ctx, hipEventRecord(a->mp_ev[2 * slot], ctx->stream));
+      HGX_TRY(mp_generate(a, (int)g0, n, (int)n_src, L, walk_seed));
+      HGX_HIP(ctx, hipEventRecord(a->mp_ev[2 * slot + 1], ctx->stream));
+      hipLaunchKernelGGL(kern, dim3(concurrent ? (n + 3) / 4 : 1), dim3(concurrent ? 256 : 64), 0,
+                         ctx->stream, A, ep, (int)g0, (int)g0 + n);
+      HGX_LAUNCH_CHECK(ctx);
+      launched++;
+    }
+  double total_ms = 0;
+  HGX_TRY(n2v_elapsed(a, &total_ms));
+  for (int64_t i = std::max<int64_t>(0, launched - kMpEvPairs); i < launched; i++)
+    HGX_TRY(collect((int)(i % kMpEvPairs)));
+  a->walk_ms = walk_ms;
+  a->train_ms = std::max(0.0, total_ms - walk_ms);
+  unsigned long long st[kMpStat * kStatSlots];
+  HGX_HIP(ctx, hipMemcpy(st, a->mp_stats.p, sizeof(st), hipMemcpyDeviceToHost));
+  a->st_mp_words = a->st_mp_pairs = a->st_mp_targets = a->st_mp_clamped = 0;
+  for (int i = 0; i < kStatSlots; i++) {
+    a->st_mp_words += (int64_t)st[kMpStat * i];
+    a->st_mp_pairs += (int64_t)st[kMpStat * i + 1];
+    a->st_mp_targets += (int64_t)st[kMpStat * i + 2];
+    a->st_mp_clamped += (int64_t)st[kMpStat * i + 3];
+  }
+  a->st_mp_walks = (int64_t)nw * epochs;
+  a->st_walks = a->st_mp_walks;
+  a->st_words = a->st_mp_words;
+  a->st_pairs = a->st_mp_pairs;
+  a->st_path_nodes = 0;
+  a->st_line_samples = a->st_line_targets = a->st_line_clamped = 0;
+  return HGX_OK;
+}
+
+extern "C" int hgx_n2v_last_mp_stats(const hgx_n2v *a, int64_t *walks, int64_t *words,
+                                     int64_t *pairs, int64_t *targets, int64_t *clamped) {
+  if (!a) return HGX_EINVAL;
+  if (walks) *walks = a->st_mp_walks;
+  if (words) *words = a->st_mp_words;
+  if (pairs) *pairs = a->st_mp_pairs;
+  if (targets) *targets = a->st_mp_targets;
+  if (clamped) *clamped = a->st_mp_clamped;
   return HGX_OK;
 }

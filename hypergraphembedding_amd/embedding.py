@@ -20,7 +20,8 @@ keys raise like the reference's ``method_not_supported`` (419-420).
 ``EmbedDeepWalk`` (deepwalk.py) is the device version of the external
 "deepwalk" baseline; the integrator binds that key, here it stays unsupported.
 ``EmbedLine`` (line.py) is the device version of the external "LINE"
-baseline, under the same rule.
+baseline, under the same rule, and ``EmbedMetapath2Vec`` (metapath2vec.py)
+that of the external "metapath2vec++" baseline.
 """
 
 import logging
@@ -43,6 +44,7 @@ from .node2vec import (EmbedNode2VecBipartide, EmbedNode2VecClique,
                        node2vec_incidence)
 from .deepwalk import EmbedDeepWalk, deepwalk_incidence
 from .line import EmbedLine, line_incidence
+from .metapath2vec import EmbedMetapath2Vec, metapath2vec_incidence
 from .svd import EmbedRandom, EmbedSvd
 
 log = logging.getLogger()
@@ -622,4 +624,5 @@ __all__ = ["Embed", "EMBEDDING_OPTIONS", "DEBUG_SUMMARY_OPTIONS",
            "EmbedAutoEncoder", "auto_encoder_incidence",
            "EmbedNode2VecBipartide", "EmbedNode2VecClique",
            "node2vec_incidence", "EmbedDeepWalk", "deepwalk_incidence",
-           "EmbedLine", "line_incidence"]
+           "EmbedLine", "line_incidence", "EmbedMetapath2Vec",
+           "metapath2vec_incidence"]

@@ -139,6 +139,12 @@ int hgx_mem_info(hgx_ctx *ctx, int64_t *free_bytes, int64_t *total_bytes);
  *                      wave (0 = a quarter of the vertex count rounded down to
  *                      a multiple of 256, in [256, 65536], default; at most
  *                      2^20)
+ *   "mp_chunk_walks"   metapath2vec: walks per chunk of the streamed corpus
+ *                      (one walk-kernel launch, then one histogram or trainer
+ *                      launch), rounded up to a multiple of 4 (0 =
+ *                      "n2v_chunk_walks"' rule, and 64 for the sequential
+ *                      trainer, default; at most 65536). The sequential
+ *                      result does not depend on it
  * Unknown keys and out-of-range values -> HGX_EINVAL. */
 int hgx_set_tuning(hgx_ctx *ctx, const char *key, int64_t value);
 
@@ -810,7 +816,49 @@ int hgx_ae_last_stats(const hgx_ae *a, double *ms, int64_t *samples,
  * HGX_EUNSUP; n_samples = 0 trains nothing. hgx_n2v_last_stats' train_ms
  * covers the run. hgx_n2v_last_line_stats: the samples, the evaluated
  * targets and those of them with |x| > 6 of the last hgx_n2v_train_line (0
- * after the other trainers). */
+ * after the other trainers).
+ *
+ * metapath2vec / metapath2vec++ trains skip-gram with negative
+ * sampling over a corpus that is never resident: walk g of n_walks =
+ * num_walks x n_src has pass g / n_src and source sources[g % n_src], L
+ * vertices (at most 256) and hgx_n2v_walks' draws at p = 1, and is generated
+ * again whenever a chunk ("mp_chunk_walks") needs it. Bipartite engines only
+ * (HGX_ESTATE on a clique engine). Every source is an edge vertex in [N, V)
+ * with a non-empty row, so a walk never stands on a vertex without a
+ * neighbour: nodes of degree 0 and empty edges are legal here. HGX_EINVAL for
+ * L < 1, num_walks < 1, n_src < 1 or a bad source; HGX_EUNSUP for L > 256 or
+ * n_walks >= 2^31.
+ *
+ * hgx_n2v_mp_walks: the walks g0 .. g0 + count - 1 alone (count x L).
+ * hgx_n2v_mp_counts: occurrences of every vertex over the whole corpus (V
+ * entries of 64 bits), chunk by chunk.
+ *
+ * hgx_n2v_set_vocab_typed: keep as hgx_n2v_set_vocab's; typed 0: cum under
+ * hgx_n2v_set_vocab's rule, one segment [0, V); typed 1: two segments, [0, N)
+ * and [N, V), each non-decreasing with a positive last entry. A negative for
+ * an output word is the first w of the segment of the word's type with
+ * cum[w] >= a uniform draw below the segment's last entry. HGX_EINVAL on a
+ * violation; a failed call sets nothing. These tables are hgx_n2v_train_mp's
+ * alone: hgx_n2v_set_vocab's stay as they are.
+ *
+ * hgx_n2v_train_mp: hgx_n2v_train's keeps, reduced windows, pair order and
+ * alpha schedule over the streamed corpus, with key (train_seed, epoch << 32
+ * | g) and counter ((position i << 8 | position j) << 4) | slot (slot 0 the
+ * keep draw, 1 the window reduction, 2 + k negative k). Per pair: l1 =
+ * syn0[w_j] held fixed; for t = w_i (label 1), then each negative (label 0,
+ * one equal to w_i skipped), in order: x = l1 . syn1[t] (the row as it
+ * stands), g = (label - s(x)) alpha with hgx_n2v_train_line's s; neu += g
+ * syn1[t]; syn1[t] += g l1; then syn0[w_j] += neu. concurrent 0: one wave
+ * trains the walks in corpus order; the result is reproducible bit for bit
+ * and does not depend on the chunk size. concurrent 1: a chunk of walks per
+ * launch on a wave each, every update a float atomic add. Needs
+ * hgx_n2v_set_vocab_typed and hgx_n2v_set_vectors (HGX_ESTATE). window < 1,
+ * negative < 0 or epochs < 0 is HGX_EINVAL; negative > 8 is HGX_EUNSUP, and so
+ * is min(2 window + 1, L) x negative > 512, the negatives staged per output
+ * word. hgx_n2v_last_stats' walk_ms is the device time of the run's walk
+ * kernels and train_ms that of the rest of the run. hgx_n2v_last_mp_stats: the
+ * walks, kept words, pairs, evaluated targets and those of them with |x| > 6
+ * of the last hgx_n2v_train_mp. */
 typedef struct hgx_n2v hgx_n2v;
 int hgx_n2v_create(hgx_ctx *ctx, int graph, int dim, hgx_n2v **out);
 int hgx_n2v_destroy(hgx_n2v *n);
@@ -841,6 +889,20 @@ int hgx_n2v_train_line(hgx_n2v *n, int order, int negative, int64_t n_samples,
                        float rho, uint64_t seed, int concurrent);
 int hgx_n2v_last_line_stats(const hgx_n2v *n, int64_t *samples,
                             int64_t *targets, int64_t *clamped);
+int hgx_n2v_mp_walks(hgx_n2v *n, int64_t n_src, const int32_t *sources,
+                     int num_walks, int L, uint64_t walk_seed, int64_t g0,
+                     int64_t count, int32_t *out);
+int hgx_n2v_mp_counts(hgx_n2v *n, int64_t n_src, const int32_t *sources,
+                      int num_walks, int L, uint64_t walk_seed,
+                      int64_t *counts_out);
+int hgx_n2v_set_vocab_typed(hgx_n2v *n, const uint32_t *keep,
+                            const int32_t *cum, int typed);
+int hgx_n2v_train_mp(hgx_n2v *n, int64_t n_src, const int32_t *sources,
+                     int num_walks, int L, int window, int negative,
+                     int epochs, float alpha, float min_alpha,
+                     uint64_t walk_seed, uint64_t train_seed, int concurrent);
+int hgx_n2v_last_mp_stats(const hgx_n2v *n, int64_t *walks, int64_t *words,
+                          int64_t *pairs, int64_t *targets, int64_t *clamped);
 
 /* ---- host utilities (bench / test data; not reference entry points) --- *
  * Power-law synthetic incidence of SURVEY.md §8(d) (C4/C5): node degree
