@@ -15,26 +15,9 @@ import pytest
 
 import oracle as O
 from hypergraphembedding_amd import _hgx
+from mlp_cases import glorot, make_case, run_both
 
 pytestmark = pytest.mark.gpu
-
-
-def glorot(shapes, rng, bias_scale=0.0):
-  parts = []
-  for k, n in shapes:
-    lim = np.sqrt(6.0 / (k + n))
-    parts += [rng.uniform(-lim, lim, k * n), rng.normal(0, bias_scale, n)]
-  return np.concatenate(parts).astype(np.float32)
-
-
-def make_case(kind, I, D, n, seed, rows=(300, 150)):
-  rng = np.random.default_rng(seed)
-  nt = rng.random((rows[0], I)).astype(np.float32)
-  et = rng.random((rows[1], I)).astype(np.float32)
-  nr = rng.integers(0, rows[0], n).astype(np.int32)
-  er = rng.integers(0, rows[1], n).astype(np.int32)
-  lab = (rng.random(n) < 1 / 6).astype(np.float32)
-  return rng, nt, et, nr, er, lab
 
 
 @pytest.fixture(scope="module")
@@ -42,25 +25,6 @@ def ctx():
   c = _hgx.Context(0)
   yield c
   c.close()
-
-
-def run_both(ctx, kind, I, D, n, epochs, seed=3, bias_scale=0.1, batch=256):
-  rng, nt, et, nr, er, lab = make_case(kind, I, D, n, seed)
-  m = _hgx.Mlp(ctx, kind, I, D)
-  w0 = glorot(m.shapes, rng, bias_scale)
-  assert w0.size == O.mlp_num_weights(kind, I, D)
-  m.set_weights(w0)
-  np.testing.assert_array_equal(m.get_weights(), w0)
-  m.set_tables(nt, et)
-  m.set_samples(nr, er, lab)
-  perms = np.stack([rng.permutation(n) for _ in range(epochs)])
-  dseed = 77
-  gl = m.fit(batch=batch, max_epochs=epochs, min_delta=-1e30, seed=dseed,
-             perms=perms)
-  wg = m.get_weights()
-  wc, cl = O.mlp_fit(kind, I, D, w0, nt, et, nr, er, lab, perms, batch=batch,
-                     min_delta=-1e30, seed=dseed)
-  return m, (nt, et, nr, er), wg, wc, gl, cl
 
 
 @pytest.mark.parametrize("kind,I,D", [(0, 40, 0), (1, 40, 24), (2, 40, 24),

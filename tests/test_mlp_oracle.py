@@ -8,90 +8,18 @@ lr * sign(g)). The dropout masks are the shared counter-based ones."""
 
 import numpy as np
 import pytest
-import torch
 
+import mlp_autograd as A
 import oracle as O
-
-M64 = (1 << 64) - 1
-
-
-def mix64(z):
-  z = (z + 0x9e3779b97f4a7c15) & M64
-  z = ((z ^ (z >> 30)) * 0xbf58476d1ce4e5b9) & M64
-  z = ((z ^ (z >> 27)) * 0x94d049bb133111eb) & M64
-  return z ^ (z >> 31)
-
-
-def rand64(seed, stream, ctr):
-  return mix64((mix64(seed ^ mix64((stream + 0x632be59bd9b4e019) & M64)) + ctr)
-               & M64)
-
-
-def drop_mask(seed, stream, M, width):
-  in4 = (width + 3) // 4 * 4
-  w64 = (in4 + 63) // 64
-  mask = np.zeros((M, width), np.float64)
-  for p in range(M):
-    for k in range(width):
-      r = rand64(seed, stream, p * w64 + (k >> 6))
-      mask[p, k] = 2.0 if (r >> (k & 63)) & 1 else 0.0
-  return mask
-
-
-def shapes_of(kind, I, D):
-  if kind == 0:
-    return [(2 * I, I), (I, 1)]
-  H = (I + D) // 2
-  s = [(I, H), (I, H), (H, D), (H, D)]
-  if kind == 2:
-    s += [(D, H), (D, H), (H, I), (H, I)]
-  return s + [(2 * D, D), (D, 1)]
+from mlp_autograd import shapes_of
+from mlp_cases import mix64, rand64  # noqa: F401 (their home is mlp_cases)
 
 
 def torch_step(kind, I, D, flat, nt, et, nr, er, lab, seed, lr, eps):
   """One Keras batch in float64 autograd; returns (new flat weights, loss)."""
-  shapes = shapes_of(kind, I, D)
-  params, off = [], 0
-  for k, n in shapes:
-    W = torch.tensor(flat[off:off + k * n].reshape(k, n), dtype=torch.float64,
-                     requires_grad=True)
-    off += k * n
-    b = torch.tensor(flat[off:off + n], dtype=torch.float64, requires_grad=True)
-    off += n
-    params.append((W, b))
-  relu, sig = torch.relu, torch.sigmoid
-  dense = lambda x, q, a: a(x @ params[q][0] + params[q][1])
-  xn = torch.tensor(nt[nr], dtype=torch.float64)
-  xe = torch.tensor(et[er], dtype=torch.float64)
-  t = torch.tensor(lab, dtype=torch.float64)
-  mse = lambda y, tt: ((y - tt) ** 2).mean(dim=-1).mean()
-  stream = 0x44000000  # epoch 0
-  if kind == 0:
-    h = dense(torch.cat([xn, xe], 1), 0, relu)
-    loss = mse(dense(h, 1, sig), t[:, None])
-  else:
-    M = len(nr)
-    dn = xn * torch.tensor(drop_mask(seed, stream, M, I))
-    de = xe * torch.tensor(drop_mask(seed, stream + 1, M, I))
-    jn = dense(dense(dn, 0, relu), 2, sig)
-    je = dense(dense(de, 1, relu), 3, sig)
-    q = 4 if kind == 1 else 8
-    y = dense(dense(torch.cat([jn, je], 1), q, relu), q + 1, sig)
-    loss = mse(y, t[:, None])
-    if kind == 2:
-      loss = 4 * loss
-      # creation order: post_n 4, post_e 5, rec_n 6, rec_e 7
-      rn = dense(dense(jn, 4, relu), 6, relu)
-      re = dense(dense(je, 5, relu), 7, relu)
-      loss = loss + mse(rn, xn) + mse(re, xe)
-  loss.backward()
-  out = []
-  for W, b in params:
-    for p in (W, b):
-      g = p.grad.numpy().ravel()
-      a = g * g
-      out.append(p.detach().numpy().ravel() - lr * g / (np.sqrt(a) + eps))
-  return np.concatenate(out), float(loss.detach())
+  r = A.fit(kind, I, D, flat, nt, et, nr, er, lab, np.arange(len(nr))[None, :],
+            batch=len(nr), lr=lr, eps=eps, seed=seed)
+  return r.w, float(r.losses[0])
 
 
 @pytest.mark.parametrize("kind", [0, 1, 2])
